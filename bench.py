@@ -11,7 +11,10 @@ One "step" = one complete pass of the hot path over one batch of synthetic input
   config 4 = the same over 8 GPUs).  Weights are random-init bf16 of the BAGEL-7B-MoT architecture (no checkpoint
   offline), inputs synthetic but resident in HBM before the timed region starts.
 
-Prints ONE JSON line (rank 0) with the contract's fields plus:
+A plain run sets up, warms up, times --steps steps and prints ONE JSON line (rank 0) with the contract's fields (metric, value, unit,
+higher_is_better, dtype, ms_per_step = milliseconds of one timed step); --dump-outputs DIR also writes what the last timed step returned
+(latents, uint8 images) as DIR/<name>.npy, float32.  With --full the line carries every other leg as well (memory, TaylorSeer, FP8, edit,
+training, understanding, parity against the oracle) and:
   roofline      achieved MFMA TFLOP/s of the dominant kernel (the persistent ping-pong GEMM, gemm_pq_kernel<*>): algorithmic 2*M*N*K FLOPs of every launch
                 in the timed region / their HIP-event durations (events on the launch stream), vs the 2.5 PFLOP/s bf16 peak;
   cpu_baseline  the oracle (CPU restatement of the reference) timed on this box's host cores on a bounded sample.
@@ -81,11 +84,47 @@ def parse():
     ap.add_argument("--job-threads", type=int, default=0, help="internal: worker mode")
     ap.add_argument("--job-node", type=int, default=-1, help="internal: worker mode (NUMA node to pin to, -1 = none)")
     ap.add_argument("--und-oracle-out", default=None, help="internal: directory of the und_depth worker whose result the understanding child compares with")
-    ap.add_argument("--wall-budget-s", type=float, default=1200.0,
-                    help="the CPU-oracle parity legs are dropped (and the line says so) once the run would pass this many seconds (the driver's limit is 1800)")
+    ap.add_argument("--wall-budget-s", type=float, default=480.0,
+                    help="the CPU-oracle parity legs are dropped (and the line says so) once the run would pass this many seconds (a --full run must end within 600)")
     ap.add_argument("--launch-check", action="store_true",
                     help="debug only: rendezvous + barrier + max-over-ranks timing + the JSON line, no model (gloo when there is no GPU)")
-    return ap.parse_args()
+    ap.add_argument("--full", action="store_true",
+                    help="everything beyond the headline figure: the B = 1 memory leg, the GEMM / attention roofline objects (events around every launch of the "
+                         "timed steps), TaylorSeer, FP8, edit, training, understanding, the CPU baseline and the oracle parity legs.  Without it a run sets up, "
+                         "warms up, times --steps steps and prints the headline line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step returned (latents, uint8 images) as DIR/<name>.npy in float32, "
+                         f"at most {DUMP_CAP_BYTES // 10 ** 6} MB in all (a fixed seeded sample of each array beyond that)")
+    args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    if not args.full:
+        # a plain run does what its headline figure needs and nothing else
+        args.no_memory_leg = args.no_taylorseer = args.no_fp8 = args.no_edit = args.no_train_forward = args.no_understanding = True
+        args.no_cpu_baseline = True
+    return args
+
+
+DUMP_CAP_BYTES = 64 * 10 ** 6
+
+
+def dump_outputs(d, arrays):
+    """--dump-outputs: every array as ``d/<name>.npy`` (float64 stays float64, everything else float32).  Past DUMP_CAP_BYTES in all, an array is replaced by a
+    fixed sample of its flattened elements (indices from a seeded generator, sorted; the same for the same shape on every run).  -> {name: description}."""
+    import numpy as np
+    os.makedirs(d, exist_ok=True)
+    arrays = {k: v.detach().to("cpu", torch.float64 if v.dtype == torch.float64 else torch.float32) for k, v in arrays.items()}
+    total = sum(v.numel() * v.element_size() for v in arrays.values())
+    info = {}
+    for k, v in arrays.items():
+        shape = list(v.shape)
+        if total > DUMP_CAP_BYTES:
+            keep = max(1, v.numel() * DUMP_CAP_BYTES // total)
+            idx = torch.randperm(v.numel(), generator=torch.Generator().manual_seed(0))[:keep].sort().values
+            v = v.reshape(-1)[idx]
+        np.save(os.path.join(d, k + ".npy"), v.numpy())
+        info[k] = {"shape": shape, "dtype": str(v.dtype).replace("torch.", ""), "sampled_elements": v.numel() if total > DUMP_CAP_BYTES else None}
+    return info
 
 
 def self_launch(args):
@@ -279,11 +318,16 @@ def wait_oracle_job(d, kind, timeout=1500.0, proc=None):
     return r
 
 
+def budget_left(args):
+    """Seconds of --wall-budget-s this run has not used yet (negative once it is over)."""
+    return args.wall_budget_s - (time.time() - T_START)
+
+
 def over_budget(args, need_s, what):
     """The wall-clock guard of the CPU-oracle legs: None, or the reason the leg is dropped."""
     used = time.time() - T_START
     if used + need_s > args.wall_budget_s:
-        return {"skipped": f"{what}: {used:.0f} s into the run, the leg needs ~{need_s:.0f} s, --wall-budget-s {args.wall_budget_s:.0f} (the driver stops bench.py at 1800 s)"}
+        return {"skipped": f"{what}: {used:.0f} s into the run, the leg needs ~{need_s:.0f} s, --wall-budget-s {args.wall_budget_s:.0f} (a --full run must end within 600 s)"}
     return None
 
 
@@ -465,16 +509,28 @@ def attn_profile_hook():
     return records, orig, timed
 
 
+def cpus_allowed():
+    """CPUs this process may use: its affinity mask, capped by OMP_NUM_THREADS where the environment sets one (a host shared by several jobs)."""
+    try:
+        n = len(os.sched_getaffinity(0))
+    except (AttributeError, OSError):
+        n = os.cpu_count() or 2
+    omp = os.environ.get("OMP_NUM_THREADS", "")
+    if omp.isdigit() and int(omp) > 0:
+        n = min(n, int(omp))
+    return max(1, n)
+
+
 def physical_cores():
-    """Physical cores of the host (SMT siblings excluded): what a bf16 GEMM-bound CPU run should use as its thread team."""
+    """Physical cores of the host (SMT siblings excluded), no more than ``cpus_allowed()``: what a bf16 GEMM-bound CPU run should use as its thread team."""
+    n = None
     try:
         import psutil
         n = psutil.cpu_count(logical=False)
-        if n:
-            return int(n)
     except Exception:
         pass
-    return max(1, (os.cpu_count() or 2) // 2)
+    n = int(n) if n else max(1, (os.cpu_count() or 2) // 2)
+    return max(1, min(n, cpus_allowed()))
 
 
 LAYER_FLOP_PER_TOKEN = 2.0 * 233046016          # linear MACs per token per MoT layer x 2 (SURVEY.md 8d)
@@ -968,7 +1024,8 @@ def cpu_baseline(args, cfg, gpu=None):
     full = None
     if gpu is not None and torch.cuda.is_available() and not args.no_full_depth:
         try:
-            full = over_budget(args, 240, "cpu_baseline.parity_at_full_depth (one Euler step of the 28-layer model through the oracle)")
+            # ~2 x 28 layer-forwards + prefill and the GPU side: 80 x the layer-forward just measured (240 s at the 3 s of a 128-thread host)
+            full = over_budget(args, 80.0 * dt, "cpu_baseline.parity_at_full_depth (one Euler step of the 28-layer model through the oracle)")
             if full is None:
                 full = full_depth_step(args, cfg, gpu["model"], gpu["tok"], gpu["ids"], threads)
                 sec_per_image = steps * full["cpu_seconds_per_euler_step"]          # measured: a whole Euler step at full depth (cond + CFG)
@@ -1048,7 +1105,7 @@ def cpu_decode_baseline(cfg, ctx):
     from oracle import bagel_oracle as O
     # one-row matrix-vector products are memory-bound and thread-sync bound: 256 threads ran them 80x SLOWER than 8 on the GPU
     # box (2.6 s vs 31 ms per layer), so the baseline uses a moderate team and reports that count as `cores`
-    threads = min(os.cpu_count(), 32)
+    threads = min(cpus_allowed(), 32)
     torch.set_num_threads(threads)
     llm = cfg["llm"]
     H, I, nh, nkv, V = llm["hidden_size"], llm["intermediate_size"], llm["num_attention_heads"], llm["num_key_value_heads"], llm["vocab_size"]
@@ -1473,7 +1530,7 @@ def understanding_subprocess(args, local, job=None):
     import subprocess
     env = dict(os.environ)
     env.update(RANK="0", WORLD_SIZE="1", LOCAL_RANK=str(local), LOCAL_WORLD_SIZE="1", BAGEL_PAUSE_PIDS=",".join(str(x) for x in Steady.pause_pids))
-    cmd = [sys.executable, os.path.abspath(__file__), "--gpus", "1", "--only-understanding"] + (["--no-cpu-baseline"] if args.no_cpu_baseline or int(os.environ.get("WORLD_SIZE", 1)) != 1 else []) + [
+    cmd = [sys.executable, os.path.abspath(__file__), "--gpus", "1", "--only-understanding", "--full"] + (["--no-cpu-baseline"] if args.no_cpu_baseline or int(os.environ.get("WORLD_SIZE", 1)) != 1 else []) + [
            "--und-new-tokens", str(args.und_new_tokens), "--und-image", str(args.und_image), "--und-batch", str(args.und_batch)] + (
            ["--no-int8"] if args.no_int8 else []) + (["--no-batched-decode"] if args.no_batched_decode else []) + (["--no-full-depth"] if args.no_full_depth else [])
     if args.layers is not None:
@@ -1482,9 +1539,9 @@ def understanding_subprocess(args, local, job=None):
         cmd += ["--und-oracle-out", job["dir"]]
     cmd += ["--wall-budget-s", str(args.wall_budget_s - (time.time() - T_START) - 250.0)]      # what is left of this run's budget, less the parent's own full-depth leg
     try:
-        r = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=1800)
-    except subprocess.TimeoutExpired:
-        return {"error": "understanding leg timed out after 1800 s"}
+        r = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=max(180.0, budget_left(args) + 60.0))
+    except subprocess.TimeoutExpired as e:
+        return {"error": f"understanding leg timed out after {e.timeout:.0f} s"}
     for line in reversed(r.stdout.strip().splitlines()):
         if line.startswith("{"):
             try:
@@ -1727,10 +1784,10 @@ def main():
             mem_b1 = {"error": repr(e)}
     for _ in range(args.warmup):
         one_step()
-    jobs_wait_s = wait_gpu_released(jobs) if jobs else 0.0          # the workers' model builds overlap the warm-up; nothing else is on the GPU from here on
+    jobs_wait_s = wait_gpu_released(jobs, timeout=max(30.0, min(300.0, budget_left(args)))) if jobs else 0.0          # the workers' model builds overlap the warm-up; nothing else is on the GPU from here on
     records, orig_gemm = [], ops.gemm
     arecords, orig_attn = [], ops.attn_planned
-    if cuda:
+    if cuda and args.full:
         records, orig_gemm, timed_gemm = gemm_profile_hook()
         ops.gemm = timed_gemm
         arecords, orig_attn, timed_attn = attn_profile_hook()
@@ -1756,6 +1813,14 @@ def main():
         per_rank_ms = [float(x) / args.steps * 1e3 for x in tt.tolist()]
         dt = float(tt.max().item())
     finite = all(torch.isfinite(x).all().item() for x in latents)
+    dumped = None
+    if args.dump_outputs:
+        # what a caller of the timed path receives from its last step: the latents generate_image returned and the decoded uint8 images
+        sfx = f"_rank{rank}" if world > 1 else ""
+        outs = {"latents" + sfx: torch.stack([x.float() for x in latents])}
+        if imgs:
+            outs["images" + sfx] = torch.stack(imgs).float()
+        dumped = {"dir": args.dump_outputs, "arrays": dump_outputs(args.dump_outputs, outs)}
     # a timed leg that went to the driver for memory is run once more -- but only in a one-rank job: the legs contain collectives (the conditioning-KV broadcast, the
     # fence's barrier), and a retry that one rank takes and another does not would leave them waiting for each other
     tries = 2 if world == 1 else 1
@@ -2005,7 +2070,7 @@ def main():
         # host time): the real request chain, the three contexts' K / V, every single forward incl. the stream-batched ones (edit_depth_step)
         try:
             job = jobs.get("edit_depth")
-            ora = wait_oracle_job(job["dir"], "edit_depth", proc=job["proc"]) if job else None
+            ora = wait_oracle_job(job["dir"], "edit_depth", timeout=max(5.0, budget_left(args)), proc=job["proc"]) if job else None
             skip = None if ora is not None else over_budget(args, 330 + 240, "edit.parity_at_depth with the oracle in this process")
             if skip is None:
                 m4, _ = build_bagel(cfg, device=dev, num_layers=EDIT_PARITY_LAYERS, with_vae=False)
@@ -2053,11 +2118,12 @@ def main():
                        # execution options in force (promoted in round 2 after measurement)
                        "options": {"cfg_batched": bool(getattr(model, "cfg_batched", False)),
                                    "und_side_path": bool(getattr(model, "cfg_batched", False) and getattr(model, "und_side_path", False))}},
-            "roofline": {"bound": "mfma", "achieved": ach, "peak": PEAK_BF16_TFLOPS, "unit": "TFLOP/s", "frac": ach / PEAK_BF16_TFLOPS,
+            "roofline": None if not args.full else {
+                         "bound": "mfma", "achieved": ach, "peak": PEAK_BF16_TFLOPS, "unit": "TFLOP/s", "frac": ach / PEAK_BF16_TFLOPS,
                          "traffic": pmc_traffic(names.get(dom, str(dom))) if (args.workload == "t2i" and args.batch == 4 and R == 1024) else None,
                          "traffic_source": PMC_SOURCE + f" ({os.path.relpath(PMC_SUMMARY, ROOT)}); null when the sources changed since", "kernel": names.get(dom, str(dom)), "launches": len(records),
                          "avg_launch_ms": ms / max(len(records), 1), "gemm_time_share": ms * 1e-3 / dt},
-            "attention": attention_object(arecords, args, R),
+            "attention": attention_object(arecords, args, R) if args.full else None,
             "outputs_finite": bool(finite),
             # the job as the collective library saw it (an all-reduce of ones at start-up) and the conditioning-KV broadcast of the timed
             # steps as rank 0 timed it (HIP events on the launch stream; null at N = 1: there is no exchange)
@@ -2067,7 +2133,7 @@ def main():
                 "calls": len(bcast_timed), "bytes_per_call": bcast_timed[0][2],
                 "ms_per_call": (sum(a.elapsed_time(b) for a, b, _ in bcast_timed) if cuda else sum((b - a) * 1e3 for a, b, _ in bcast_timed)) / len(bcast_timed),
                 "what": "conditioning KV of the shared prompt: rank 0 prefills, one flat bf16 buffer [L][2][rows][nkv*D] + an int64 header to every rank"},
-            "memory": {"resident": resident_weight_bytes(model, vae) if cuda and not args.standins else None,
+            "memory": {"resident": resident_weight_bytes(model, vae) if cuda and not args.standins and args.full else None,
                        "t2i_b1_request": mem_b1,
                        "headline_timed_region": dict(mem_head.report, what=f"the {args.steps} timed steps at B = {B}/GPU (fp32 VAE decode included)"),
                        "note": "peak_mem_gb = torch.cuda.max_memory_allocated after reset_peak_memory_stats (live tensor bytes: weights + packed copies + the leg's "
@@ -2084,7 +2150,10 @@ def main():
             "taylorseer": ts,
             "fp8_gen_expert": fp8,
             "training_forward": trainf,
+            "full": bool(args.full),
         }
+        if dumped is not None:
+            out["dumped_outputs"] = dumped
         if args.workload == "t2i":
             # the whole path against the MFMA roof: denoise FLOPs (linear + attention of the 98 forwards, SURVEY.md 8d: 5.904 PFLOP
             # per image at the default shapes) over the whole step time incl. prefill, glue and VAE decode
@@ -2110,7 +2179,7 @@ def main():
             try:
                 for j in jobs.values():                    # the CPU baseline is TIMED: no worker may still be on the host cores
                     try:
-                        j["proc"].wait(timeout=600)
+                        j["proc"].wait(timeout=max(5.0, budget_left(args)))
                     except Exception:
                         j["proc"].kill()
                 gpu = None if (args.layers is not None or args.workload != "t2i") else dict(model=model, tok=tok, ids=ids)

@@ -248,7 +248,7 @@ def test_bench_one_step_on_two_gloo_ranks():
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
     env["CUDA_VISIBLE_DEVICES"] = env["HIP_VISIBLE_DEVICES"] = ""
     env["OMP_NUM_THREADS"] = "2"
-    common = ["--standins", "--batch", "2", "--resolution", "64", "--num-timesteps", "4", "--prompt-tokens", "6"]
+    common = ["--standins", "--batch", "2", "--resolution", "64", "--num-timesteps", "4", "--prompt-tokens", "6", "--full"]      # --full: the training legs too
 
     def run(n, steps, warmup):
         r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", str(n), "--steps", str(steps), "--warmup", str(warmup)] + common,
@@ -273,6 +273,41 @@ def test_bench_one_step_on_two_gloo_ranks():
     one = run(1, 1, 0)
     assert one["n_gpus"] == 1 and one["ranks_seen"] == 1 and one["broadcast"] is None and one["collective_backend"] is None
     assert one["latents_checksum"] == two["latents_checksum"], "rank 0 of the 2-rank job must reproduce the 1-rank job's samples"
+
+
+def test_bench_plain_run_is_lean_and_dumps_outputs(tmp_path):
+    """A plain run (no --full) times --steps steps and prints the headline line without the extra legs; --dump-outputs writes what the last
+    timed step returned (latents, uint8 images) as float32 .npy files, the same arrays on every run with the same arguments."""
+    import json
+    import subprocess
+    import sys
+    import numpy as np
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
+    env["CUDA_VISIBLE_DEVICES"] = env["HIP_VISIBLE_DEVICES"] = ""
+    env["OMP_NUM_THREADS"] = "2"
+
+    def run(d):
+        r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "0", "--standins", "--batch", "2",
+                            "--resolution", "64", "--num-timesteps", "4", "--prompt-tokens", "6", "--dump-outputs", str(d)],
+                           env=env, capture_output=True, text=True, timeout=600)
+        assert r.returncode == 0, r.stderr[-3000:]
+        lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
+        assert len(lines) == 1, r.stdout[-2000:]
+        return json.loads(lines[0])
+    out = run(tmp_path / "a")
+    assert out["steps"] == 3 and out["ms_per_step"] > 0 and out["full"] is False
+    assert abs(out["value"] - 2 / (out["ms_per_step"] / 1e3)) < 1e-6 * out["value"]
+    for leg in ("training_forward", "taylorseer", "fp8_gen_expert", "edit", "understanding", "cpu_baseline", "roofline", "attention"):
+        assert out.get(leg) is None, leg
+    lat = np.load(tmp_path / "a" / "latents.npy")
+    img = np.load(tmp_path / "a" / "images.npy")
+    assert lat.dtype == np.float32 and img.dtype == np.float32 and lat.shape[0] == 2 and img.shape == (2, 64, 64, 3)
+    assert [float(x) for x in lat.astype(np.float64).reshape(2, -1).sum(1)] == out["latents_checksum"]
+    assert img.min() >= 0 and img.max() <= 255 and np.array_equal(img, np.floor(img))
+    run(tmp_path / "b")
+    for name in ("latents", "images"):
+        assert np.array_equal(np.load(tmp_path / "a" / f"{name}.npy"), np.load(tmp_path / "b" / f"{name}.npy")), name
 
 
 def _ddp_worker(rank, ws, port, q):

@@ -13,8 +13,10 @@ if [ -z "$SKIP_PYTEST" ]; then
   done
   ( timeout 300 python __graft_entry__.py smoke ) > gpurun_out/smoke.log 2>&1; tail -2 gpurun_out/smoke.log
 fi
-( time timeout 2400 python bench.py --steps ${STEPS:-2} --warmup 1 ) > gpurun_out/bench.log 2>&1
-grep "^{" gpurun_out/bench.log | cut -c1-400
+BENCH_LOG=${BENCH_LOG:-$ROOT/bench_logs/bench_full.log}
+mkdir -p "$(dirname "$BENCH_LOG")"
+( time timeout 2400 python bench.py --full --steps ${STEPS:-2} --warmup 1 ) > "$BENCH_LOG" 2>&1
+grep "^{" "$BENCH_LOG" | cut -c1-400
 if [ -z "$SKIP_PROF" ]; then
   cd /tmp
   ( timeout 900 rocprofv3 --kernel-trace --stats -d $ROOT/gpurun_out/prof -o bench -- python $ROOT/bench.py --steps 1 --warmup 0 --no-memory-leg --no-cpu-baseline --no-understanding --no-taylorseer --no-edit --no-fp8 --no-train-forward ) > $ROOT/gpurun_out/bench_prof.log 2>&1
