@@ -642,12 +642,13 @@ __device__ __forceinline__ i32x8_t cat_frag(const bf16x8_t& lo, const bf16x8_t& 
     return __builtin_shufflevector(a, b, 0, 1, 2, 3, 4, 5, 6, 7);
 }
 
-// max over the 16 lanes of a DPP row (all 16 end up with it): quads, half-row mirror, row mirror
-__device__ __forceinline__ float pq_rowmax16(float x) {
-    x = fmaxf(x, __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(x), 0xB1, 0xf, 0xf, true)));     // quad_perm [1, 0, 3, 2]
-    x = fmaxf(x, __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(x), 0x4E, 0xf, 0xf, true)));     // quad_perm [2, 3, 0, 1]
-    x = fmaxf(x, __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(x), 0x141, 0xf, 0xf, true)));    // row_half_mirror
-    x = fmaxf(x, __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(x), 0x140, 0xf, 0xf, true)));    // row_mirror
+// max over the 16 lanes of a DPP row (all 16 end up with it): quads, half-row mirror, row mirror.  On the bit patterns of |values|: non-negative floats
+// order like unsigned integers, and a NaN (above +Inf) survives where fmaxf would drop it
+__device__ __forceinline__ unsigned pq_rowmax16(unsigned x) {
+    x = max(x, (unsigned)__builtin_amdgcn_update_dpp(0, (int)x, 0xB1, 0xf, 0xf, true));     // quad_perm [1, 0, 3, 2]
+    x = max(x, (unsigned)__builtin_amdgcn_update_dpp(0, (int)x, 0x4E, 0xf, 0xf, true));     // quad_perm [2, 3, 0, 1]
+    x = max(x, (unsigned)__builtin_amdgcn_update_dpp(0, (int)x, 0x141, 0xf, 0xf, true));    // row_half_mirror
+    x = max(x, (unsigned)__builtin_amdgcn_update_dpp(0, (int)x, 0x140, 0xf, 0xf, true));    // row_mirror
     return x;
 }
 
@@ -1017,25 +1018,30 @@ __global__ __launch_bounds__(512, 2) void gemm_pq_kernel(const GemmParams p) {
                     asm volatile("" ::"v"(v));
 #else
                     if constexpr (QOUT) {
-                        // 8 bf16 of one row -> 8 e4m3 bytes with the caller's scale (clamped to the format's range: a row that grew past the delayed scale's
-                        // headroom saturates instead of turning into NaN codes), and this row's max |value| for the next step's scale
+                        // 8 bf16 of one row -> 8 e4m3 bytes with the caller's scale (finite values clamped to the format's range: a row that grew past the
+                        // delayed scale's headroom saturates instead of turning into NaN codes; NaN / Inf values and a NaN scale give NaN codes, as the exact
+                        // path's quantiser does), and this row's max |value| for the next step's scale (NaN-propagating: an integer max of the bit patterns)
                         const bool ok = col_ok && m0 + it * 32 + rb < Mg;
                         float f[8];
 #pragma unroll
                         for (int e = 0; e < 4; ++e) { f[2 * e] = __uint_as_float(v[e] << 16); f[2 * e + 1] = __uint_as_float(v[e] & 0xffff0000u); }
-                        float am = fmaxf(fmaxf(fabsf(f[0]), fabsf(f[1])), fmaxf(fabsf(f[2]), fabsf(f[3])));
-                        am = fmaxf(am, fmaxf(fmaxf(fabsf(f[4]), fabsf(f[5])), fmaxf(fabsf(f[6]), fabsf(f[7]))));
-                        am = pq_rowmax16(ok ? am : 0.f);                       // the 16 lanes of a DPP row hold the 128 columns of one tile row
+                        unsigned am = 0u;
+#pragma unroll
+                        for (int e = 0; e < 8; ++e) am = max(am, __float_as_uint(fabsf(f[e])));
+                        am = pq_rowmax16(ok ? am : 0u);                        // the 16 lanes of a DPP row hold the 128 columns of one tile row
                         const float inv = cinv[it];
 #pragma unroll
-                        for (int e = 0; e < 8; ++e) f[e] = fminf(fmaxf(f[e] * inv, -448.f), 448.f);
+                        for (int e = 0; e < 8; ++e) {
+                            const float y = f[e] * inv;
+                            f[e] = (fabsf(f[e]) <= 3.40282347e38f && y == y) ? fminf(fmaxf(y, -448.f), 448.f) : __builtin_nanf("");
+                        }
                         int w0 = 0, w1 = 0;
                         w0 = __builtin_amdgcn_cvt_pk_fp8_f32(f[0], f[1], w0, false);
                         w0 = __builtin_amdgcn_cvt_pk_fp8_f32(f[2], f[3], w0, true);
                         w1 = __builtin_amdgcn_cvt_pk_fp8_f32(f[4], f[5], w1, false);
                         w1 = __builtin_amdgcn_cvt_pk_fp8_f32(f[6], f[7], w1, true);
                         if (ok) *(u32x2_t*)(p.Cq + (long)crow[it] * p.ldcq + oc) = (u32x2_t){(unsigned)w0, (unsigned)w1};
-                        if (qs == 0 && m0 + it * 32 + rb < Mg) atomicMax(p.cmax + crow[it], __float_as_uint(am));
+                        if (qs == 0 && m0 + it * 32 + rb < Mg) atomicMax(p.cmax + crow[it], am);
                     } else {
                         if (col_ok && m0 + it * 32 + rb < Mg) *(u32x4_t*)(p.C + (long)crow[it] * p.ldc + oc) = v;
                     }
@@ -1483,7 +1489,7 @@ extern "C" int bagel_gemm_fp8_bf16(const void* Aq, int64_t lda_bytes, const floa
 
 // The gate/up projection of the FP8 gen expert with the SwiGLU result written as e4m3 bytes (no bf16 round trip, no stand-alone quantiser pass in front of the
 // down projection): Cq[c_rows[i], :N/2] = e4m3(clamp(swiglu(...) / cs[c_rows[i]], +-448)), cmax[c_rows[i]] = max(cmax[..], max_n |swiglu(...)|) (fp32 bits,
-// atomicMax).  DELAYED scaling: `cs` is chosen by the caller before the values exist (bagel_fp8_delayed_scales: from the previous denoise step's row maxima,
+// atomicMax).  Only finite values are clamped: NaN / Inf values (and a NaN scale) give NaN codes and a NaN / Inf row maximum, as the exact path does.  DELAYED scaling: `cs` is chosen by the caller before the values exist (bagel_fp8_delayed_scales: from the previous denoise step's row maxima,
 // with headroom), `cmax` collects this step's maxima for the next one.  oracle/fp8.py restates the scheme.
 extern "C" int bagel_gemm_fp8_swiglu_q8(const void* Aq, int64_t lda_bytes, const float* sa, const void* Wq, int64_t ldw_bytes, const float* sw,
                                         const int32_t* a_rows, const int32_t* c_rows, int32_t M, void* Cq, int64_t ldcq_bytes, const float* cs,

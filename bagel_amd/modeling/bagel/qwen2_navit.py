@@ -797,18 +797,38 @@ class Fp8DelayedScales:
     """State of the DELAYED row scales of the FP8 gen expert's SwiGLU output across the forwards of ONE stream set of a denoise loop (the same latent rows at
     consecutive timesteps): per layer and physical row the max |value| the last forward saw (collected by the gate/up GEMM's epilogue with atomicMax) and the
     scale in use.  ``margin`` = headroom factor between what was seen and what fits the e4m3 range (2.0: a row may double between two steps before it
-    saturates -- saturates, not overflows: the epilogue clamps).  ``oracle/fp8.py::DelayedScales`` restates the scheme."""
+    saturates -- saturates, not overflows: the epilogue clamps finite values; NaN / Inf stay non-finite).  ``oracle/fp8.py::DelayedScales`` restates the scheme.
+
+    The rule: a forward of Euler step ``i`` quantises with delayed scales only if the forward of step ``i - 1`` refreshed THIS state's row maxima (``step``, the
+    Euler step of the last refresh, is ``i - 1``).  Otherwise it takes the exact path, which leaves fresh maxima behind.  That covers the first step, the first
+    full step after TaylorSeer steps (a skipped forward runs no layer and refreshes nothing), and the steps where ``cfg_interval`` switches between the
+    stream-batched state and the per-stream ones: the state that runs did not run in the step before, and no rows are handed over between the two.
+    ``saturated`` counts the rows found past their scale's range (bagel_fp8_delayed_scales) when the next delayed step builds its scales."""
 
     def __init__(self, margin=2.0):
         self.margin = float(margin)
-        self.amax = self.scale = None
-        self.primed = False
+        self.amax = self.scale = self.saturated = None
+        self.step = None
+
+    @property
+    def primed(self):
+        return self.step is not None
+
+    def fresh(self, step):
+        """May the forward of Euler step ``step`` use the delayed scales?"""
+        return self.step is not None and self.step == step - 1
 
     def fit(self, layers, rows, device):
         if self.amax is None or self.amax.shape != (layers, rows) or self.amax.device != torch.device(device):
             self.amax = torch.zeros((layers, rows), dtype=torch.float32, device=device)
             self.scale = torch.ones((layers, rows), dtype=torch.float32, device=device)
-            self.primed = False
+            self.step = None
+        if self.saturated is None or self.saturated.device != torch.device(device):
+            self.saturated = torch.zeros((1,), dtype=torch.int32, device=device)
+
+    def saturated_rows(self):
+        """Rows (summed over layers and steps) whose maximum exceeded 448 x the delayed scale they were quantised with (synchronises)."""
+        return 0 if self.saturated is None else int(self.saturated.item())
 
 
 class MoTEngine:
@@ -965,8 +985,10 @@ class MoTEngine:
         return self._fp8
 
     def forward(self, seq, plan: ForwardPlan, mode="und", cache: NaiveCache = None, update=True, causal=True,
-                num_layers=None, taylor=None, final_norm=True, gen_quant=None, fp8_state=None):
+                num_layers=None, taylor=None, final_norm=True, gen_quant=None, fp8_state=None, fp8_step=None):
         """Qwen2Model.forward_inference (qwen2_navit.py:1018-1092).  ``seq`` is not modified.
+        ``fp8_state`` / ``fp8_step``: the delayed-scale state of this stream set and the Euler step of this forward (Fp8DelayedScales; None = the step after
+        the state's last refresh).
         ``taylor``: a TaylorSeerState (cache_utils/taylorseer.py) -> the TaylorSeer hooks of :1034-1037,1057-1061,
         1086-1087 are active: a 'full' step runs the layers and refreshes the feature cache, a 'Taylor' step replaces
         the whole layer stack by the cached extrapolation."""
@@ -1019,6 +1041,7 @@ class MoTEngine:
         # skinny GEMMs, their q/k/v rows are scattered into the fused projection buffer before the attention and their attention
         # rows gathered after it.  Same operators, same rounding points; only the GEMM kernel that serves those rows differs.
         fp8 = delayed = None
+        use_delayed = False
         if gen_quant is not None and nl > 0 and gen:
             if gen_quant != "fp8":
                 raise NotImplementedError(f"gen_weight_quant={gen_quant!r}: only 'fp8' (OCP e4m3, row-wise scales) is built")
@@ -1034,11 +1057,14 @@ class MoTEngine:
                 fw = self._ws_fp8[plan.M] = dict(hq=u8(plan.M, self.H), sh=f32(), aq=u8(plan.M, nq * dp), sa=f32(), cq=u8(plan.M, self.I), sc=f32())
             # DELAYED scaling of the SwiGLU output (Fp8DelayedScales: a denoise loop hands the same state to every step of one forward stream set): from the
             # second forward on the gate/up GEMM writes e4m3 bytes itself, scaled by what the previous step's rows reached -- no bf16 round trip of the
-            # [M, I] activation and no quantiser pass in front of the down projection.  The first forward (no history) and callers without a state take the
-            # exact path and, with a state, leave their row maxima behind.
+            # [M, I] activation and no quantiser pass in front of the down projection.  A forward whose state was not refreshed by the previous Euler step
+            # (the rule of Fp8DelayedScales) and callers without a state take the exact path and, with a state, leave their row maxima behind.
             if fp8_state is not None:
                 fp8_state.fit(nl, plan.M, self.device)
                 delayed = fp8_state
+                if fp8_step is None:
+                    fp8_step = 0 if delayed.step is None else delayed.step + 1
+                use_delayed = delayed.fresh(fp8_step)
         side = bool(gen_attn and (plan.und_side or fp8 is not None) and nl > 0 and 2 <= plan.n_text <= ops.SKINNY_MAX_ROWS)
         if side:
             nt = plan.n_text
@@ -1101,8 +1127,9 @@ class MoTEngine:
                     ops.rmsnorm(xu, P.ln_post[0], hu, self.eps)
                     ops.rmsnorm_fp8(x, P.ln_post[1], fw["hq"], fw["sh"], self.eps)
                     ops.gemm(hu, P.wgu[0], actu, epilogue=ops.EPI_SWIGLU16)
-                    if delayed is not None and delayed.primed:
-                        ops.fp8_delayed_scales(delayed.amax[li], delayed.scale[li], rows=plan.vae_idx, n=plan.n_vae, margin=delayed.margin)
+                    if delayed is not None and use_delayed:
+                        ops.fp8_delayed_scales(delayed.amax[li], delayed.scale[li], rows=plan.vae_idx, n=plan.n_vae, margin=delayed.margin,
+                                               saturated=delayed.saturated)
                         ops.gemm_fp8_swiglu_q8(fw["hq"], fw["sh"], Q["wgu"][0], Q["wgu"][1], fw["cq"], delayed.scale[li], delayed.amax[li], rows=plan.vae_idx, M=plan.n_vae)
                         ops.gemm(actu, P.wd[0], xu, residual=xu)
                         ops.gemm_fp8(fw["cq"], delayed.scale[li], Q["wd"][0], Q["wd"][1], x, rows=plan.vae_idx, M=plan.n_vae, residual=x)
@@ -1110,8 +1137,9 @@ class MoTEngine:
                     ops.gemm_fp8(fw["hq"], fw["sh"], Q["wgu"][0], Q["wgu"][1], act, rows=plan.vae_idx, M=plan.n_vae, epilogue=ops.EPI_SWIGLU16)
                     ops.gemm(actu, P.wd[0], xu, residual=xu)
                     ops.quantize_rows_fp8(act, fw["cq"], fw["sc"])
-                    if delayed is not None:          # the exact scale is rowmax / 448: leave the row maxima for the next forward
+                    if delayed is not None:          # the exact scale is rowmax / 448: leave the row maxima (and the scale in use) for the next forward
                         torch.mul(fw["sc"], 448.0, out=delayed.amax[li])
+                        delayed.scale[li].copy_(fw["sc"])
                     ops.gemm_fp8(fw["cq"], fw["sc"], Q["wd"][0], Q["wd"][1], x, rows=plan.vae_idx, M=plan.n_vae, residual=x)
                     continue
                 ops.gemm(att, C=x, residual=x, **gen_only(P.wo))
@@ -1129,7 +1157,7 @@ class MoTEngine:
         if side:
             ops.copy_rows(xu, x, nt, self.H, dst_rows=plan.text_idx)
         if delayed is not None:
-            delayed.primed = True            # every layer has left its rows' maxima behind: the next forward of this stream set quantises with them
+            delayed.step = fp8_step          # every layer has left its rows' maxima behind: the forward of the next Euler step may quantise with them
         if taylor is not None:
             if not skip_layers:
                 taylor.update(x)

@@ -424,7 +424,7 @@ def gemm_fp8(Aq, sa, Wq, sw, C, *, bias=None, rows=None, M=None, residual=None, 
 def gemm_fp8_swiglu_q8(Aq, sa, Wq, sw, Cq, cs, cmax, *, rows=None, M=None):
     """The FP8 gen expert's gate/up projection with the SwiGLU result written as e4m3 bytes under a DELAYED row scale: Cq[rows] =
     e4m3(clamp(swiglu(sa[rows] * sw * (Aq[rows] @ Wq^T)) / cs[rows], +-448)), cmax[rows] = max(cmax[rows], rowmax |swiglu(..)|) (fp32 bit patterns);
-    see bagel_gemm_fp8_swiglu_q8 / fp8_delayed_scales."""
+    NaN / Inf values (and a NaN scale) give NaN codes and a non-finite row maximum instead of being clamped; see bagel_gemm_fp8_swiglu_q8 / fp8_delayed_scales."""
     _req(Aq, torch.uint8, "gemm_fp8_swiglu_q8.Aq"); _req(Wq, torch.uint8, "gemm_fp8_swiglu_q8.Wq"); _req(Cq, torch.uint8, "gemm_fp8_swiglu_q8.Cq")
     for t, n in ((sa, "sa"), (sw, "sw"), (cs, "cs"), (cmax, "cmax")):
         _req(t, torch.float32, "gemm_fp8_swiglu_q8." + n)
@@ -440,15 +440,18 @@ def gemm_fp8_swiglu_q8(Aq, sa, Wq, sw, Cq, cs, cmax, *, rows=None, M=None):
     return Cq
 
 
-def fp8_delayed_scales(amax, scale, *, rows=None, n=None, margin=2.0):
-    """scale[r] = margin * amax[r] / 448 (1.0 where amax is 0) and amax[r] = 0 for the rows in use: the step between two denoise forwards of the delayed
-    scaling (bagel_fp8_delayed_scales); ``amax`` holds non-negative fp32 values collected by atomicMax on their bit patterns."""
+def fp8_delayed_scales(amax, scale, *, rows=None, n=None, margin=2.0, saturated=None):
+    """scale[r] = margin * amax[r] / 448 (1.0 where amax is 0, NaN where it is NaN or Inf) and amax[r] = 0 for the rows in use: the step between two denoise
+    forwards of the delayed scaling (bagel_fp8_delayed_scales); ``amax`` holds non-negative fp32 values collected by atomicMax on their bit patterns.
+    ``saturated``: optional int32 counter (device), +1 per row whose amax was not within 448 x the scale[r] it replaces."""
     _req(amax, torch.float32, "fp8_delayed_scales.amax"); _req(scale, torch.float32, "fp8_delayed_scales.scale")
     if rows is not None:
         _req(rows, torch.int32, "fp8_delayed_scales.rows")
+    if saturated is not None:
+        _req(saturated, torch.int32, "fp8_delayed_scales.saturated")
     if n is None:
         n = rows.numel() if rows is not None else amax.numel()
-    check(lib().bagel_fp8_delayed_scales(_ptr(amax), _ptr(scale), _ptr(rows), n, float(margin), _stream()), "bagel_fp8_delayed_scales")
+    check(lib().bagel_fp8_delayed_scales(_ptr(amax), _ptr(scale), _ptr(rows), n, float(margin), _ptr(saturated), _stream()), "bagel_fp8_delayed_scales")
     return scale
 
 

@@ -545,7 +545,9 @@ def forward_flow(W, cfg, x_t, timestep, gi, cache, cfg_text=None, cfg_img=None, 
     seq[gi["packed_vae_token_indexes"]] = h
     vae_idx, text_idx = gi["packed_vae_token_indexes"], gi["packed_text_indexes"]
 
-    def run(cache_, pos_ids, q_idx, kv_lens, kv_idx, ts=None):
+    def run(cache_, pos_ids, q_idx, kv_lens, kv_idx, ts=None, stream=0):
+        if FP8_DELAYED is not None:
+            FP8_DELAYED.select(stream)
         mode = "gen" if "Mo" in cfg["llm"].get("layer_module", "Qwen2MoTDecoderLayer") else "und"     # use_moe, bagel.py:808-815
         out = llm_forward(W, cfg["llm"], seq, gi["packed_seqlens"], pos_ids, q_idx, cache_, kv_lens, kv_idx,
                           False, False, mode, vae_idx, text_idx, taylor=ts, taylor_last_layer_only=taylor_last_layer_only)
@@ -557,10 +559,10 @@ def forward_flow(W, cfg, x_t, timestep, gi, cache, cfg_text=None, cfg_img=None, 
               gi["packed_key_value_indexes"], ty[0])
     if cfg_text_scale > 1.0:
         c = cfg_text
-        v_ct = run(c["cache"], c["position_ids"], c["query_indexes"], c["key_values_lens"], c["key_value_indexes"], ty[1])
+        v_ct = run(c["cache"], c["position_ids"], c["query_indexes"], c["key_values_lens"], c["key_value_indexes"], ty[1], 1)
     if cfg_img_scale > 1.0:
         c = cfg_img
-        v_ci = run(c["cache"], c["position_ids"], c["query_indexes"], c["key_values_lens"], c["key_value_indexes"], ty[2])
+        v_ci = run(c["cache"], c["position_ids"], c["query_indexes"], c["key_values_lens"], c["key_value_indexes"], ty[2], 2)
 
     if parts is not None:          # checker hook (bench.py full-depth parity): the single-forward velocities before the CFG combine
         parts["v_cond"] = v_t
@@ -576,8 +578,9 @@ def forward_flow(W, cfg, x_t, timestep, gi, cache, cfg_text=None, cfg_img=None, 
 @_explicit_casts
 def generate_image(W, cfg, gi, cache, cfg_text=None, cfg_img=None, num_timesteps=24, timestep_shift=1.0,
                    cfg_renorm_min=0.0, cfg_renorm_type="global", cfg_interval=(0, 1), cfg_text_scale=1.0,
-                   cfg_img_scale=1.0, max_steps=None, enable_taylorseer=False, taylor_last_layer_only=False):
-    """Bagel.generate_image, bagel.py:644-754 (``enable_taylorseer``: :680-689)."""
+                   cfg_img_scale=1.0, max_steps=None, enable_taylorseer=False, taylor_last_layer_only=False, fp8_batched=True):
+    """Bagel.generate_image, bagel.py:644-754 (``enable_taylorseer``: :680-689).  ``fp8_batched``: only read with FP8_DELAYED -- whether the product
+    runs the CFG steps as one stream-batched forward (model.cfg_batched), which decides the state whose history a step's delayed scales come from."""
     taylor = tuple(TaylorState(num_timesteps) for _ in range(3)) if enable_taylorseer else None
     x_t = gi["packed_init_noises"]
     ts, dts = flow_schedule(num_timesteps, timestep_shift)
@@ -585,12 +588,12 @@ def generate_image(W, cfg, gi, cache, cfg_text=None, cfg_img=None, num_timesteps
         if max_steps is not None and i >= max_steps:
             break
         timestep = torch.tensor([t] * x_t.shape[0])
-        if FP8_DELAYED is not None:
-            FP8_DELAYED.begin_step()
         if t > cfg_interval[0] and t <= cfg_interval[1]:
             s_t, s_i = cfg_text_scale, cfg_img_scale
         else:
             s_t, s_i = 1.0, 1.0
+        if FP8_DELAYED is not None:
+            FP8_DELAYED.begin_step(i, batched=fp8_batched and s_t > 1.0)
         v_t = forward_flow(W, cfg, x_t, timestep, gi, cache, cfg_text, cfg_img, s_t, s_i, cfg_renorm_min,
                            cfg_renorm_type, taylor, taylor_last_layer_only)
         x_t = x_t - v_t.to(x_t.device) * dts[i]

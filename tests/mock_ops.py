@@ -773,13 +773,80 @@ def chw_f32_to_u8(src):
     return v.to(torch.uint8).permute(1, 2, 0).contiguous()
 
 
+def quantize_rows_fp8(X, q=None, scale=None):
+    """FP8 option (oracle/fp8.py restates the kernels): the exact row-wise quantiser."""
+    from oracle import fp8 as F8
+    qq, ss = F8.quantize_rows_fp8(X)
+    if q is None:
+        return qq, ss
+    q[:X.shape[0], :X.shape[1]] = qq
+    scale[:X.shape[0]] = ss
+    return q, scale
+
+
+def rmsnorm_fp8(x, w, q, scale, eps):
+    y = torch.empty_like(x)
+    rmsnorm(x, w, y, eps)
+    return quantize_rows_fp8(y, q, scale)
+
+
+def _gemm_fp8_rows(Aq, sa, Wq, sw, r, swiglu):
+    f8 = torch.float8_e4m3fn
+    acc = (Aq[r].view(f8).double() @ Wq.view(f8).double().t()).float() * (sa[r][:, None] * sw[None, :])
+    if swiglu:
+        a = acc.view(acc.shape[0], Wq.shape[0] // 32, 2, 16)
+        g, u = _bf(a[:, :, 0].reshape(acc.shape[0], -1)), _bf(a[:, :, 1].reshape(acc.shape[0], -1))
+        return _bf(_bf(F.silu(g.float())).float() * u.float())
+    return acc
+
+
+def gemm_fp8(Aq, sa, Wq, sw, C, *, bias=None, rows=None, M=None, residual=None, epilogue=0):
+    if M is None:
+        M = rows.numel() if rows is not None else Aq.shape[0]
+    r = _rows(rows, M, M)
+    y = _gemm_fp8_rows(Aq, sa, Wq, sw, r, epilogue == 3)
+    if epilogue != 3:
+        if bias is not None:
+            y = y + bias.float()
+        y = _bf(y)
+    if residual is not None:
+        y = _bf(y.float() + residual[r, :y.shape[1]].float())
+    C[r, :y.shape[1]] = y
+    return C
+
+
+def gemm_fp8_swiglu_q8(Aq, sa, Wq, sw, Cq, cs, cmax, *, rows=None, M=None):
+    from oracle import fp8 as F8
+    if M is None:
+        M = rows.numel() if rows is not None else Aq.shape[0]
+    r = _rows(rows, M, M)
+    q, amax = F8.quantize_rows_delayed(_gemm_fp8_rows(Aq, sa, Wq, sw, r, True), cs[r])
+    Cq[r, :q.shape[1]] = q
+    cmax[r] = torch.maximum(cmax[r], amax)
+    return Cq
+
+
+def fp8_delayed_scales(amax, scale, *, rows=None, n=None, margin=2.0, saturated=None):
+    from oracle import fp8 as F8
+    if n is None:
+        n = rows.numel() if rows is not None else amax.numel()
+    r = _rows(rows, n, n)
+    a = amax[r]
+    if saturated is not None:
+        saturated += int((~(a <= 448.0 * scale[r])).sum())
+    scale[r] = F8.delayed_scales(a, margin)
+    amax[r] = 0.0
+    return scale
+
+
 _NAMES = ["gemm", "gemv", "gemv_mb", "gemm_skinny", "rmsnorm", "layernorm", "rope_table", "qknorm_rope", "v_transpose", "attn_varlen",
           "copy_rows", "f32_to_bf16", "timestep_sinusoid", "flow_add", "add_table_rows", "cfg_stage1", "cfg_stage2_euler",
           "argmax", "require_gpu_bf16", "rope2d", "taylor_update", "taylor_eval", "attn_varlen_ranges", "flow_mix", "flow_add_rows",
           "mse_rows", "cross_entropy", "argmax_into", "sample_gumbel_into", "rope_table_into", "decode_qkv_post", "kv_append_paged", "attn_decode_paged", "attn_decode_fused", "quantize_rows_mxfp4", "gemv_w4", "quantize_nf4", "gemv_nf4", "dequantize_nf4", "quantize_rows_i8", "dequantize_rows_i8", "gemv_w8",
           "decode_advance", "require_gpu_f32", "attn_planned", "conv_gemm_f32", "groupnorm_f32", "softmax_rows_f32", "vae_reparam_f32", "conv_gemm_bf16", "groupnorm_bf16", "groupnorm_bf16_workspace_floats", "softmax_rows_bf16", "vae_reparam_bf16", "chw_bf16_to_u8",
           "vae_unscale_f32", "resample_u8", "u8_to_chw_f32", "chw_f32_to_u8", "transpose", "rmsnorm_bwd", "layernorm_bwd", "qknorm_rope_bwd", "swiglu_bwd",
-          "act_bwd", "swiglu_fwd", "cross_entropy_bwd", "mse_rows_bwd", "rows_segment_sum", "colsum", "attn_bwd_blockmask"]
+          "act_bwd", "swiglu_fwd", "cross_entropy_bwd", "mse_rows_bwd", "rows_segment_sum", "colsum", "attn_bwd_blockmask",
+          "quantize_rows_fp8", "rmsnorm_fp8", "gemm_fp8", "gemm_fp8_swiglu_q8", "fp8_delayed_scales"]
 
 
 def install(monkeypatch):

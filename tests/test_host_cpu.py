@@ -221,6 +221,13 @@ def test_vae_launch_wrappers_match_the_header(monkeypatch):
     ops.gemv_mb(b(4, 128), b(64, 128), b(4, 64), M=4)
     assert calls == ["bagel_conv_gemm_bf16"] * 2 + ["bagel_groupnorm_bf16", "bagel_softmax_rows_bf16", "bagel_vae_reparam_bf16", "bagel_chw_bf16_to_u8",
                      "bagel_gemv_mb_bf16"]
+    # the FP8 option's delayed scales (with and without the saturated-row counter) and the fp8-output gate/up projection
+    del calls[:]
+    ops.fp8_delayed_scales(f(8), f(8), rows=torch.arange(4, dtype=torch.int32), margin=2.0, saturated=torch.zeros(1, dtype=torch.int32))
+    ops.fp8_delayed_scales(f(8), f(8))
+    u8 = lambda *s: torch.zeros(*s, dtype=torch.uint8)  # noqa: E731
+    ops.gemm_fp8_swiglu_q8(u8(4, 256), f(4), u8(64, 256), f(64), u8(4, 32), f(4), f(4), rows=torch.arange(4, dtype=torch.int32))
+    assert calls == ["bagel_fp8_delayed_scales"] * 2 + ["bagel_gemm_fp8_swiglu_q8"]
 
 
 def test_ops_gemm_routing_of_the_vit_epilogues_and_small_row_counts(monkeypatch):
