@@ -622,15 +622,21 @@ class Bagel(nn.Module):
         Embeddings, lm_head, norms, biases, ViT / connector / VAE stay bf16 like the library leaves non-Linear and skipped modules.
         ``release_bf16=True`` frees the bf16 projection weights afterwards (28.3 -> 8.6 GB at 7B with "nf4"); reload the checkpoint to go back.
         An option that changes results, like the reference's modes; parity with bitsandbytes' binaries is unpinned (oracle/nf4.py).
+        "mxfp4" is the chip's own 4-bit mode: OCP-MX FP4 codes with one E8M0 scale per 32 weights (oracle/mxfp4.py), consumed by the block-scaled MFMA
+        directly -- every decoder projection of prefill, denoise loop and decode computes FP8 row-quantised activations x MXFP4 weights with fp32
+        accumulation (``ops.gemm_w4`` / ``ops.gemv_w4``), nothing is de-quantised into bf16 scratch (0.27 x the bf16 projection bytes resident).  It
+        needs hidden, intermediate and padded attention widths that are multiples of 128 and is refused before anything is switched otherwise.
         "int8" -- the reference's mode 3, LLM.int8 with fp16 outlier columns (app.py:126-131) -- is NOT built and is refused by name.
         With ``release_bf16=True`` the model can no longer produce a state dict (``state_dict()`` raises: the projection weights are gone) and any later
         invalidation of the packed weights (``.to()``, a second call) needs a NEW model build + checkpoint load."""
-        from .qwen2_navit import LLM_INT8_NOT_BUILT
+        from .qwen2_navit import LLM_INT8_NOT_BUILT, mxfp4_refusal
         if kind == "int8":
             raise NotImplementedError(LLM_INT8_NOT_BUILT)
-        if kind not in ("nf4", "int8_rowwise"):
-            raise NotImplementedError(f"quantize_language_model(kind={kind!r}): 'nf4' and 'int8_rowwise' are built")
+        if kind not in ("nf4", "int8_rowwise", "mxfp4"):
+            raise NotImplementedError(f"quantize_language_model(kind={kind!r}): 'nf4', 'int8_rowwise' and 'mxfp4' are built")
         lm = self.language_model
+        if kind == "mxfp4" and mxfp4_refusal(lm.model.config):          # refused before anything is switched or released
+            raise NotImplementedError(mxfp4_refusal(lm.model.config))
         self._ensure_bf16()
         if hasattr(lm.model, "release_train_buffers"):
             lm.model.release_train_buffers()          # (tape pool of a previous training step: tens of GB at 7B, train_step.py)

@@ -737,12 +737,14 @@ class _PackedLayer:
 class _StoredLayers:
     """``MoTEngine.layers`` of a quantised engine: a sequence whose items are materialised on access.  Layer i's packed bf16 matrices are
     de-quantised into scratch set i % 2 (two sets: a consumer may still hold the previous layer's view while it asks for the next), small
-    tensors (biases, norm weights) are kept as they are.  Only the inference forwards iterate it; training and the fp8 option refuse."""
+    tensors (biases, norm weights) are kept as they are.  Only the inference forwards iterate it; training and the fp8 option refuse.
+    kind "mxfp4": nothing is ever materialised -- an item carries the (codes, scale bytes) pairs themselves, which ``ops.gemm_w4`` consumes on the
+    block-scaled MFMA (MoTEngine.forward's layer body for this mode) and the Lq = 1 decode streams through ``ops.gemv_w4``: no scratch sets."""
     MATS = ("wqkv", "wo", "wgu", "wd")
 
     def __init__(self, eng, modules, kind):
         self.eng, self.kind = eng, kind
-        quant = ops.quantize_nf4 if kind == "nf4" else ops.quantize_rows_i8
+        quant = {"nf4": ops.quantize_nf4, "int8_rowwise": ops.quantize_rows_i8, "mxfp4": ops.quantize_rows_mxfp4}[kind]
         self.stored, self.small = [], []
         for L in modules:
             P = eng._pack_layer(L)
@@ -763,6 +765,14 @@ class _StoredLayers:
 
     def __getitem__(self, i):
         st = self.stored[i]
+        if self.kind == "mxfp4":
+            P = _PackedLayer()
+            for name in self.MATS:
+                setattr(P, name, st[name])                     # [(codes, scales) per expert]: never a matrix
+            for n, v in self.small[i].items():
+                setattr(P, n, v)
+            P.wt = {}
+            return P
         slot = i % 2
         if self.scratch[slot] is None:
             self.scratch[slot] = {name: [torch.empty((q.shape[0], q.shape[1] * (2 if self.kind == "nf4" else 1)), dtype=BF16, device=q.device)
@@ -791,6 +801,16 @@ class _StoredLayers:
 
     def resident_bytes(self):
         return sum(q.numel() * q.element_size() + sc.numel() * sc.element_size() for st in self.stored for ms in st.values() for q, sc in ms)
+
+
+def mxfp4_refusal(cfg):
+    """Why ``weight_store = "mxfp4"`` cannot serve a language model of this geometry (None: it can): the block-scaled MFMA consumes 128-deep k-steps,
+    so every projection's row length -- H, I and the padded attention width -- has to be a multiple of 128."""
+    H, I, nq = cfg.hidden_size, cfg.intermediate_size, cfg.num_attention_heads
+    for n, k in (("hidden_size", H), ("intermediate_size", I), ("num_attention_heads x padded head_dim", nq * padded_head_dim(H // nq))):
+        if k % 128:
+            return f"weight_store='mxfp4' needs {n} = {k} to be a multiple of 128 (one k-step of the block-scaled MFMA)"
+    return None
 
 
 class Fp8DelayedScales:
@@ -860,8 +880,13 @@ class MoTEngine:
         # codes.  Biases, norm weights, embeddings, lm_head stay bf16 (llm_int8_skip_modules / the library never touches non-Linear weights).
         if weight_store == "int8":
             raise NotImplementedError(LLM_INT8_NOT_BUILT)
-        if weight_store not in (None, "nf4", "int8_rowwise"):
-            raise NotImplementedError(f"weight_store={weight_store!r}: 'nf4' (bitsandbytes NF4: blocks of 64, fp32 absmax) and 'int8_rowwise' (row-wise absmax) are built")
+        # "mxfp4": OCP-MX FP4 codes + E8M0 block scales (oracle/mxfp4.py) consumed by the matrix pipe directly -- every projection of prefill, denoise
+        # loop and decode is FP8 row-quantised activations x MXFP4 weights (ops.gemm_w4 / ops.gemv_w4); nothing is de-quantised into scratch.
+        if weight_store not in (None, "nf4", "int8_rowwise", "mxfp4"):
+            raise NotImplementedError(f"weight_store={weight_store!r}: 'nf4' (bitsandbytes NF4: blocks of 64, fp32 absmax), 'int8_rowwise' (row-wise absmax) "
+                                      "and 'mxfp4' (OCP-MX FP4 blocks of 32 x FP8 activations) are built")
+        if weight_store == "mxfp4" and mxfp4_refusal(cfg):
+            raise NotImplementedError(mxfp4_refusal(cfg))
         self.weight_store = weight_store
         if weight_store is None:
             self.layers = [self._pack_layer(l) for l in model.layers]
@@ -969,6 +994,17 @@ class MoTEngine:
     def plan(self, query_lens, position_ids, **kw):
         return ForwardPlan(self.device, query_lens, position_ids, inv_freq=self.model.rotary_emb.inv_freq(self.device), **kw)
 
+    def _fp8_workspace(self, M):
+        """e4m3 images + row scales of the three activations a layer quantises (norm output, attention output, SwiGLU output), cached per row count."""
+        fw = self._ws_fp8.get(M)
+        if fw is None:
+            u8 = lambda *s: torch.empty(s, dtype=torch.uint8, device=self.device)  # noqa: E731
+            f32 = lambda: torch.empty((M,), dtype=torch.float32, device=self.device)  # noqa: E731
+            if len(self._ws_fp8) > 3:
+                self._ws_fp8.pop(next(iter(self._ws_fp8)))
+            fw = self._ws_fp8[M] = dict(hq=u8(M, self.H), sh=f32(), aq=u8(M, self.nq * self.dp), sa=f32(), cq=u8(M, self.I), sc=f32())
+        return fw
+
     def fp8_weights(self):
         """OCP e4m3 copies (row-wise absmax scales) of the gen expert's four projections, quantised on first use (option
         ``gen_weight_quant = "fp8"``: the MI355X counterpart of the reference's quantised load modes, app.py:114-131)."""
@@ -1048,13 +1084,7 @@ class MoTEngine:
             if not (gen_attn and 2 <= plan.n_text <= ops.SKINNY_MAX_ROWS):
                 raise NotImplementedError("gen_weight_quant='fp8' needs the MoT layer kind and 2..64 marker rows (they take the bf16 side path)")
             fp8 = self.fp8_weights()
-            fw = self._ws_fp8.get(plan.M)
-            if fw is None:
-                u8 = lambda *s: torch.empty(s, dtype=torch.uint8, device=self.device)  # noqa: E731
-                f32 = lambda: torch.empty((plan.M,), dtype=torch.float32, device=self.device)  # noqa: E731
-                if len(self._ws_fp8) > 3:
-                    self._ws_fp8.pop(next(iter(self._ws_fp8)))
-                fw = self._ws_fp8[plan.M] = dict(hq=u8(plan.M, self.H), sh=f32(), aq=u8(plan.M, nq * dp), sa=f32(), cq=u8(plan.M, self.I), sc=f32())
+            fw = self._fp8_workspace(plan.M)
             # DELAYED scaling of the SwiGLU output (Fp8DelayedScales: a denoise loop hands the same state to every step of one forward stream set): from the
             # second forward on the gate/up GEMM writes e4m3 bytes itself, scaled by what the previous step's rows reached -- no bf16 round trip of the
             # [M, I] activation and no quantiser pass in front of the down projection.  A forward whose state was not refreshed by the previous Euler step
@@ -1065,7 +1095,27 @@ class MoTEngine:
                 if fp8_step is None:
                     fp8_step = 0 if delayed.step is None else delayed.step + 1
                 use_delayed = delayed.fresh(fp8_step)
-        side = bool(gen_attn and (plan.und_side or fp8 is not None) and nl > 0 and 2 <= plan.n_text <= ops.SKINNY_MAX_ROWS)
+        # weight_store = "mxfp4": every projection is FP8 row-quantised activations x the stored MXFP4 codes (ops.gemm_w4, one call per expert row group;
+        # any row count, so the marker rows need no side path).  The activation of a projection goes bf16 -> e4m3 + row scale right in front of it
+        # (norm output, attention output, SwiGLU output: exact scales, no delayed scaling in this mode) -- the arithmetic oracle/mxfp4.py::gemv_w4 states.
+        w4 = self.weight_store == "mxfp4" and nl > 0
+        if w4:
+            fw = self._fp8_workspace(plan.M)
+
+            def w4_norm(ln, two):
+                if two:
+                    ops.rmsnorm(x, ln[0], h, self.eps, w1=ln[1], expert=expert)
+                    ops.quantize_rows_fp8(h, fw["hq"], fw["sh"])
+                else:
+                    ops.rmsnorm_fp8(x, ln[0], fw["hq"], fw["sh"], self.eps)
+
+            def w4_mm(aq, sa, w, C, two, bias=None, **kw):
+                if not two:
+                    return ops.gemm_w4(aq, sa, w[0][0], w[0][1], C, bias=None if bias is None else bias[0], M=plan.M, **kw)
+                for e, (rows, n) in enumerate(((plan.text_idx, plan.n_text), (plan.vae_idx, plan.n_vae))):
+                    if n:
+                        ops.gemm_w4(aq, sa, w[e][0], w[e][1], C, bias=None if bias is None else bias[e], rows=rows, M=n, **kw)
+        side = bool(gen_attn and (plan.und_side or fp8 is not None) and nl > 0 and 2 <= plan.n_text <= ops.SKINNY_MAX_ROWS and not w4)
         if side:
             nt = plan.n_text
             sw = self._ws_side.get(nt)
@@ -1080,9 +1130,12 @@ class MoTEngine:
                 return dict(W0=w[1], bias0=None if b is None else b[1], a_rows0=plan.vae_idx, c_rows0=plan.vae_idx, M0=plan.n_vae)
         for li in range(nl):
             P = self.layers[li]
-            if fp8 is None:
+            if fp8 is None and not w4:
                 ops.rmsnorm(x, P.ln_in[0], h, self.eps, w1=P.ln_in[1] if gen_attn else None, expert=expert if gen_attn else None)
-            if side:
+            if w4:
+                w4_norm(P.ln_in, gen_attn)
+                w4_mm(fw["hq"], fw["sh"], P.wqkv, qkv, gen_attn, bias=P.bqkv)
+            elif side:
                 ops.rmsnorm(xu, P.ln_in[0], hu, self.eps)
                 ops.gemm(hu, P.wqkv[0], qu, bias0=P.bqkv[0])
                 ops.copy_rows(qu, qkv, nt, qu.shape[1], dst_rows=plan.text_idx)
@@ -1118,6 +1171,14 @@ class MoTEngine:
                 if cache is None:
                     raise ValueError("update_past_key_values=True needs a NaiveCache")
                 cache.store(li, k_v, v_v, plan.q_lens, plan.ctx_lens, nkv, hd, dp, plan.new_dst, plan.ctx_dst)
+            if w4:
+                ops.quantize_rows_fp8(att, fw["aq"], fw["sa"])
+                w4_mm(fw["aq"], fw["sa"], P.wo, x, gen_attn, residual=x)
+                w4_norm(P.ln_post, gen_attn)
+                w4_mm(fw["hq"], fw["sh"], P.wgu, act, gen, epilogue=ops.EPI_SWIGLU16)
+                ops.quantize_rows_fp8(act, fw["cq"], fw["sc"])
+                w4_mm(fw["cq"], fw["sc"], P.wd, x, gen, residual=x)
+                continue
             if side:
                 ops.copy_rows(att, au, nt, au.shape[1], src_rows=plan.text_idx)
                 ops.gemm(au, P.wo[0], xu, residual=xu)

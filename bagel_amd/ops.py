@@ -560,6 +560,29 @@ def gemv_w4(A, Wq, Ws, C, *, bias=None, residual=None, epilogue=EPI_NONE, M=None
     return C
 
 
+def gemm_w4(Aq, sa, Wq, Ws, C, *, bias=None, rows=None, M=None, residual=None, epilogue=EPI_NONE):
+    """C[rows] = epilogue(sa[rows] * (Aq[rows] @ dequant(Wq, Ws)^T)): e4m3 activations with row scales (``quantize_rows_fp8`` /
+    ``rmsnorm_fp8``) x MXFP4 weights (``quantize_rows_mxfp4``) on the block-scaled MFMA, any number of rows; ``rows`` = the row list of the
+    one row group (gather of A / scatter of C and the residual); see bagel_gemm_w4_bf16."""
+    _req(Aq, torch.uint8, "gemm_w4.Aq"); _req(Wq, torch.uint8, "gemm_w4.Wq"); _req(Ws, torch.uint8, "gemm_w4.Ws"); _req(C, BF16, "gemm_w4.C")
+    _req(sa, torch.float32, "gemm_w4.sa")
+    N, K = Wq.shape[0], Wq.shape[1] * 2
+    if Aq.shape[-1] != K or Ws.shape[0] != N or sa.numel() < Aq.shape[0]:
+        raise BagelHipError("gemm_w4: shape mismatch")
+    if rows is not None:
+        _req(rows, torch.int32, "gemm_w4.rows")
+    if M is None:
+        M = rows.numel() if rows is not None else Aq.shape[0]
+    if residual is not None:
+        _req(residual, BF16, "gemm_w4.residual")
+    if bias is not None:
+        _req(bias, BF16, "gemm_w4.bias")
+    check(lib().bagel_gemm_w4_bf16(_ptr(Aq), Aq.stride(0), _ptr(sa), _ptr(Wq), Wq.stride(0), _ptr(Ws), Ws.stride(0), _ptr(bias), _ptr(rows),
+                                   _ptr(rows), M, _ptr(residual), _ld(residual) if residual is not None else 0, _ptr(C), _ld(C), N, K,
+                                   epilogue, _stream()), "bagel_gemm_w4_bf16")
+    return C
+
+
 KV_PAGE = 64          # tokens per KV page (BAGEL_KV_PAGE in decode.hip)
 DECODE_CHUNK = 64     # smallest keys-per-split the library may use (DEC_CH 128, or 64 with BAGEL_DEC_CH=64): sizes the workspace
 

@@ -262,6 +262,15 @@ int bagel_quantize_rows_mxfp4(const void* W, int64_t ldw, void* q, int64_t ldq_b
 int bagel_gemv_w4_bf16(const void* A, int64_t lda, const void* Wq, int64_t ldq_bytes, const void* Ws, int64_t lds_bytes, const void* bias,
                        const void* R, int64_t ldr, void* C, int64_t ldc, const void* norm_w, float eps, int32_t M, int32_t N,
                        int32_t K, int32_t epilogue, bagel_stream_t stream);
+/* The same product for ANY number of rows (the whole-model load mode weight_store = "mxfp4": prefill and denoise forwards on the codes the
+ * decode kernel streams): C[c_rows[i], :] = epilogue(sa[a_rows[i]] * sum_k Aq[a_rows[i], k] * (E2M1(code[n, k]) * 2^(sb[n, k/32] - 127))),
+ * Aq = e4m3 bytes with one fp32 scale per row (bagel_quantize_rows_fp8 / bagel_rmsnorm_fp8), Wq / Ws exactly as bagel_quantize_rows_mxfp4
+ * writes them, fp32 accumulation on v_mfma_scale_f32_16x16x128_f8f6f4.  One row group (optional int32 row list: gather of A, scatter of C
+ * and the residual; rows of C outside the list are not written); epilogues none (+bias, +residual) / SwiGLU16 (3) with the rounding
+ * points of bagel_gemm_bf16.  M >= 1; K % 128 == 0; N % 8 == 0 (SwiGLU: N % 32); lda / ldq / lds in bytes. */
+int bagel_gemm_w4_bf16(const void* Aq, int64_t lda_bytes, const float* sa, const void* Wq, int64_t ldq_bytes, const void* Ws,
+                       int64_t lds_bytes, const void* bias, const int32_t* a_rows, const int32_t* c_rows, int32_t M, const void* R,
+                       int64_t ldr, void* C, int64_t ldc, int32_t N, int32_t K, int32_t epilogue, bagel_stream_t stream);
 
 /* FP8 (OCP e4m3) path for the gen-expert GEMMs of the denoise forward (the MI355X-native counterpart of the reference's quantised
  * load modes, app.py:114-131 -- an OPTION that changes results; bf16 is the default).
