@@ -213,54 +213,79 @@ extern "C" int bagel_conv_gemm_f32(const float* in, int64_t ld_in, const float* 
 }
 
 // ---------------------------------------------------------------------------------------------------------
-// GroupNorm over NHWC fp32: stats per (image, group) with a shifted two-moment accumulation (pivot = first element of
-// the group, common to every partial -> partials add exactly; no catastrophic cancellation), fixed-order reduction.
+// GroupNorm over NHWC fp32: stats per (image, group).  Every slice of a group makes two passes over its own elements (the second one
+// hits the cache): their mean first, then the sum of squares AROUND THAT MEAN, so no term is larger than the slice's own spread -- a
+// shift by one sampled element (the group's first, as before) cancels catastrophically when that element is an outlier: rstd then
+// loses eps * (pivot distance / sigma)^2.  The (count, mean, M2) triples of the slices are merged pairwise (Chan et al.) in slice
+// order; counts follow from the slice index, so a partial is (mean, M2).  Fixed reduction order throughout: run-to-run deterministic.
 // ---------------------------------------------------------------------------------------------------------
 #define GN_SLICES 64
+__device__ __forceinline__ float gn_block_sum(float v, float* red) {          // 256 threads, fixed tree; every thread gets the total
+    red[threadIdx.x] = v;
+    __syncthreads();
+    for (int s = 128; s > 0; s >>= 1) {
+        if (threadIdx.x < s) red[threadIdx.x] += red[threadIdx.x + s];
+        __syncthreads();
+    }
+    const float t = red[0];
+    __syncthreads();
+    return t;
+}
+
+// (sum of d, sum of d^2) with d = x - m0 and m0 the first-pass mean  ->  (mean, M2) of cnt elements; the first-order term repairs m0's rounding
+__device__ __forceinline__ void gn_slice_moments(float m0, float s1, float s2, float cnt, float* o) {
+    const float corr = cnt > 0.f ? s1 / cnt : 0.f;
+    o[0] = m0 + corr;
+    o[1] = fmaxf(s2 - s1 * corr, 0.f);
+}
+
+struct GnMoments { float n, mean, m2; };
+__device__ __forceinline__ void gn_merge(GnMoments& a, float nb, float mb, float m2b) {
+    if (nb <= 0.f) return;
+    const float n = a.n + nb, d = mb - a.mean;
+    a.mean += d * (nb / n);
+    a.m2 += m2b + d * d * (a.n * nb / n);
+    a.n = n;
+}
+
 __global__ __launch_bounds__(256) void gn_stats_kernel(const float* __restrict__ x, float* __restrict__ partial, int HW, int C, int G) {
     const int b = blockIdx.z, g = blockIdx.y, sl = blockIdx.x;
     const int cpg = C / G;
     const float* xb = x + (long)b * HW * C + g * cpg;
-    const float pivot = xb[0];
     const long n = (long)HW * cpg;
     const long per = (n + GN_SLICES - 1) / GN_SLICES;
     const long lo = sl * per, hi = min(n, lo + per);
+    const float cnt = (float)max(hi - lo, 0L);
+    __shared__ float red[256];
+    float s0 = 0.f;
+    for (long i = lo + threadIdx.x; i < hi; i += 256) {
+        const long pix = i / cpg;
+        s0 += xb[pix * C + (int)(i - pix * cpg)];
+    }
+    s0 = gn_block_sum(s0, red);
+    const float m0 = cnt > 0.f ? s0 / cnt : 0.f;
     float s1 = 0.f, s2 = 0.f;
     for (long i = lo + threadIdx.x; i < hi; i += 256) {
         const long pix = i / cpg;
-        const int c = (int)(i - pix * cpg);
-        const float d = xb[pix * C + c] - pivot;
+        const float d = xb[pix * C + (int)(i - pix * cpg)] - m0;
         s1 += d; s2 += d * d;
     }
-    __shared__ float r1[256], r2[256];
-    r1[threadIdx.x] = s1; r2[threadIdx.x] = s2;
-    __syncthreads();
-    for (int s = 128; s > 0; s >>= 1) {
-        if (threadIdx.x < s) { r1[threadIdx.x] += r1[threadIdx.x + s]; r2[threadIdx.x] += r2[threadIdx.x + s]; }
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) {
-        float* o = partial + (((long)b * G + g) * GN_SLICES + sl) * 2;
-        o[0] = r1[0]; o[1] = r2[0];
-    }
+    s1 = gn_block_sum(s1, red);
+    s2 = gn_block_sum(s2, red);
+    if (threadIdx.x == 0) gn_slice_moments(m0, s1, s2, cnt, partial + (((long)b * G + g) * GN_SLICES + sl) * 2);
 }
 
-// (mean, rstd) per (image, group) from the slice partials, fixed order.
-__global__ void gn_finalize_kernel(const float* __restrict__ x, const float* __restrict__ partial, float* __restrict__ stats, int HW,
-                                   int C, int G, float eps, int BG) {
+// (mean, rstd) per (image, group) from the slice partials, merged in slice order.
+__global__ void gn_finalize_kernel(const float* __restrict__ partial, float* __restrict__ stats, int HW, int C, int G, float eps, int BG) {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= BG) return;
-    const int b = i / G, g = i - b * G;
-    const int cpg = C / G;
     const float* pp = partial + (long)i * GN_SLICES * 2;
-    float s1 = 0.f, s2 = 0.f;
-    for (int k = 0; k < GN_SLICES; ++k) { s1 += pp[2 * k]; s2 += pp[2 * k + 1]; }
-    const float n = (float)HW * (float)cpg;
-    const float pivot = x[(long)b * HW * C + g * cpg];
-    const float md = s1 / n;
-    const float var = fmaxf(s2 / n - md * md, 0.f);
-    stats[2 * i] = pivot + md;
-    stats[2 * i + 1] = rsqrtf(var + eps);
+    const long n = (long)HW * (C / G);
+    const long per = (n + GN_SLICES - 1) / GN_SLICES;
+    GnMoments a = {0.f, 0.f, 0.f};
+    for (int k = 0; k < GN_SLICES; ++k) gn_merge(a, (float)max(min(n, (k + 1) * per) - k * per, 0L), pp[2 * k], pp[2 * k + 1]);
+    stats[2 * i] = a.mean;
+    stats[2 * i + 1] = rsqrtf(a.m2 / a.n + eps);
 }
 
 __global__ __launch_bounds__(256) void gn_apply_kernel(const float* __restrict__ x, float* __restrict__ y, const float* __restrict__ stats,
@@ -295,7 +320,7 @@ extern "C" int bagel_groupnorm_f32(const float* x, float* y, float* partial_ws, 
     // workspace: [B*G*GN_SLICES*2] partials followed by [B*G*2] stats
     float* stats = partial_ws + (long)B * groups * GN_SLICES * 2;
     hipLaunchKernelGGL(gn_stats_kernel, dim3(GN_SLICES, groups, B), dim3(256), 0, stream, x, partial_ws, HW, C, groups);
-    hipLaunchKernelGGL(gn_finalize_kernel, dim3(ceil_div(B * groups, 64)), dim3(64), 0, stream, x, partial_ws, stats, HW, C, groups, eps, B * groups);
+    hipLaunchKernelGGL(gn_finalize_kernel, dim3(ceil_div(B * groups, 64)), dim3(64), 0, stream, partial_ws, stats, HW, C, groups, eps, B * groups);
     const long total4 = (long)HW * C / 4;
     const int blocks = (int)min((long)ceil_div(total4, 256), 2048L);
     hipLaunchKernelGGL(gn_apply_kernel, dim3(blocks, B), dim3(256), 0, stream, x, y, stats, gamma, beta, HW, C, groups, swish);
@@ -601,69 +626,90 @@ extern "C" int bagel_conv_gemm_bf16(const void* in, int64_t ld_in, const void* w
 }
 
 #define GN_BF16_SLICES 1024
-// ---- GroupNorm of a bf16 NHWC tensor: fp32 statistics (same shifted two-moment scheme and fixed-order reduction as the fp32 kernels) ----
+// ---- GroupNorm of a bf16 NHWC tensor: fp32 statistics (per-slice mean, squares around it, Chan merge in slice order: as the fp32 kernels) ----
 __global__ __launch_bounds__(256) void gn_stats_bf16_kernel(const bf16_t* __restrict__ x, float* __restrict__ partial, int HW, int C, int G, int S) {
     const int b = blockIdx.z, g = blockIdx.y, sl = blockIdx.x;
     const int cpg = C / G;
     const bf16_t* xb = x + (long)b * HW * C + g * cpg;
-    const float pivot = bf2f(xb[0]);
     const long n = (long)HW * cpg;
     const long per = (n + S - 1) / S;
     const long lo = sl * per, hi = min(n, lo + per);
+    const float cnt = (float)max(hi - lo, 0L);
+    __shared__ float red[256];
+    float s0 = 0.f;
+    for (long i = lo + threadIdx.x; i < hi; i += 256) {
+        const long pix = i / cpg;
+        s0 += bf2f(xb[pix * C + (int)(i - pix * cpg)]);
+    }
+    s0 = gn_block_sum(s0, red);
+    const float m0 = cnt > 0.f ? s0 / cnt : 0.f;
     float s1 = 0.f, s2 = 0.f;
     for (long i = lo + threadIdx.x; i < hi; i += 256) {
         const long pix = i / cpg;
-        const int c = (int)(i - pix * cpg);
-        const float d = bf2f(xb[pix * C + c]) - pivot;
+        const float d = bf2f(xb[pix * C + (int)(i - pix * cpg)]) - m0;
         s1 += d; s2 += d * d;
     }
-    __shared__ float r1[256], r2[256];
-    r1[threadIdx.x] = s1; r2[threadIdx.x] = s2;
-    __syncthreads();
-    for (int s = 128; s > 0; s >>= 1) {
-        if (threadIdx.x < s) { r1[threadIdx.x] += r1[threadIdx.x + s]; r2[threadIdx.x] += r2[threadIdx.x + s]; }
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) {
-        float* o = partial + (((long)b * G + g) * S + sl) * 2;
-        o[0] = r1[0]; o[1] = r2[0];
-    }
+    s1 = gn_block_sum(s1, red);
+    s2 = gn_block_sum(s2, red);
+    if (threadIdx.x == 0) gn_slice_moments(m0, s1, s2, cnt, partial + (((long)b * G + g) * S + sl) * 2);
 }
 
-// one wave per (image, group): lane l sums slices l, l + 64, ...; the 64 lane sums meet in a fixed butterfly order
-__global__ __launch_bounds__(64) void gn_finalize_bf16_kernel(const bf16_t* __restrict__ x, const float* __restrict__ partial, float* __restrict__ stats,
-                                                              int HW, int C, int G, float eps, int BG, int S) {
-    const int i = blockIdx.x;
-    const int b = i / G, g = i - b * G;
-    const int cpg = C / G;
+// one wave per (image, group): lane l merges its run of consecutive slices, lane 0 then merges the 64 runs in order.  Slice k holds
+// ``mult`` elements for each of its units [k per, min(U, (k + 1) per)): units are elements (U = HW * C / G, mult = 1) under the per-group
+// statistics kernel and pixels (U = HW, mult = C / G) under the coalesced one.
+__global__ __launch_bounds__(64) void gn_finalize_bf16_kernel(const float* __restrict__ partial, float* __restrict__ stats, long U, int mult, float eps,
+                                                              int S) {
+    const int i = blockIdx.x, lane = threadIdx.x;
     const float* pp = partial + (long)i * S * 2;
-    float s1 = 0.f, s2 = 0.f;
-    for (int k = threadIdx.x; k < S; k += 64) { s1 += pp[2 * k]; s2 += pp[2 * k + 1]; }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) { s1 += __shfl_xor(s1, o); s2 += __shfl_xor(s2, o); }
-    if (threadIdx.x) return;
-    const float n = (float)HW * (float)cpg;
-    const float pivot = bf2f(x[(long)b * HW * C + g * cpg]);
-    const float md = s1 / n;
-    const float var = fmaxf(s2 / n - md * md, 0.f);
-    stats[2 * i] = pivot + md;
-    stats[2 * i + 1] = rsqrtf(var + eps);
+    const long per = (U + S - 1) / S;
+    const int run = (S + 63) >> 6;
+    GnMoments a = {0.f, 0.f, 0.f};
+    for (int k = lane * run; k < min(S, (lane + 1) * run); ++k)
+        gn_merge(a, (float)(max(min(U, (k + 1) * per) - k * per, 0L) * mult), pp[2 * k], pp[2 * k + 1]);
+    __shared__ float rn[64], rm[64], r2[64];
+    rn[lane] = a.n; rm[lane] = a.mean; r2[lane] = a.m2;
+    __syncthreads();
+    if (lane) return;
+    for (int l = 1; l < 64; ++l) gn_merge(a, rn[l], rm[l], r2[l]);
+    stats[2 * i] = a.mean;
+    stats[2 * i + 1] = rsqrtf(a.m2 / a.n + eps);
 }
 
 // Coalesced statistics pass: a thread owns one 16-byte chunk (8 channels) of a pixel row and walks the pixels of its slice, so a wave reads
 // whole 128-byte lines (the per-group form above reads C / G channels out of every 2 C-byte pixel row: 8 of 256 bytes at C = 128); the
-// per-channel partial sums meet in LDS and are folded into per-group sums in a fixed order.  Needs 256 % (C / 8) == 0.
+// per-channel partial sums meet in LDS and are folded into per-group sums in a fixed order -- once for the slice's group means, once more
+// for the moments around them.  Needs 256 % (C / 8) == 0.
 __global__ __launch_bounds__(256) void gn_stats_rows_bf16_kernel(const bf16_t* __restrict__ x, float* __restrict__ partial, int HW, int C, int G, int S) {
     const int b = blockIdx.y, sl = blockIdx.x, tid = threadIdx.x;
     const int cpg = C / G, CH = C >> 3, ppi = 256 / CH;
     const int ck = tid % CH, pr = tid / CH;
     const bf16_t* xb = x + (long)b * HW * C;
     const int per = (HW + S - 1) / S;
-    const int lo = sl * per, hi = min(HW, lo + per);
+    const int lo = min(HW, sl * per), hi = min(HW, lo + per);
+    const float cnt = (float)(hi - lo) * (float)cpg;
+    __shared__ float red[256][17];
+    __shared__ float gm[2048];                       // C <= 2048 here, so G <= 2048
     float piv[8], s1[8], s2[8];
 #pragma unroll
+    for (int e = 0; e < 8; ++e) s1[e] = 0.f;
+    for (int p = lo + pr; p < hi; p += ppi) {
+        const u32x4_t v = *(const u32x4_t*)(xb + (long)p * C + ck * 8);
+#pragma unroll
+        for (int e = 0; e < 8; ++e) s1[e] += (e & 1) ? hi2f(v[e >> 1]) : lo2f(v[e >> 1]);
+    }
+#pragma unroll
+    for (int e = 0; e < 8; ++e) red[tid][e] = s1[e];
+    __syncthreads();
+    for (int g = tid; g < G; g += 256) {
+        float a1 = 0.f;
+        for (int c = g * cpg; c < (g + 1) * cpg; ++c)
+            for (int r = 0; r < ppi; ++r) a1 += red[r * CH + (c >> 3)][c & 7];
+        gm[g] = cnt > 0.f ? a1 / cnt : 0.f;
+    }
+    __syncthreads();
+#pragma unroll
     for (int e = 0; e < 8; ++e) {
-        piv[e] = bf2f(xb[((ck * 8 + e) / cpg) * cpg]);
+        piv[e] = gm[(ck * 8 + e) / cpg];
         s1[e] = s2[e] = 0.f;
     }
     for (int p = lo + pr; p < hi; p += ppi) {
@@ -674,7 +720,6 @@ __global__ __launch_bounds__(256) void gn_stats_rows_bf16_kernel(const bf16_t* _
             s1[e] += d; s2[e] += d * d;
         }
     }
-    __shared__ float red[256][17];
 #pragma unroll
     for (int e = 0; e < 8; ++e) { red[tid][e] = s1[e]; red[tid][8 + e] = s2[e]; }
     __syncthreads();
@@ -682,8 +727,7 @@ __global__ __launch_bounds__(256) void gn_stats_rows_bf16_kernel(const bf16_t* _
         float a1 = 0.f, a2 = 0.f;
         for (int c = g * cpg; c < (g + 1) * cpg; ++c)
             for (int r = 0; r < ppi; ++r) { a1 += red[r * CH + (c >> 3)][c & 7]; a2 += red[r * CH + (c >> 3)][8 + (c & 7)]; }
-        float* o = partial + (((long)b * G + g) * S + sl) * 2;
-        o[0] = a1; o[1] = a2;
+        gn_slice_moments(gm[g], a1, a2, cnt, partial + (((long)b * G + g) * S + sl) * 2);
     }
 }
 
@@ -737,12 +781,13 @@ extern "C" int bagel_groupnorm_bf16(const void* x, void* y, float* partial_ws, c
     float* ab = stats + (long)B * groups * 2;
     const int CH = C / 8;
     const int S = (int)std::max(1L, std::min((long)GN_BF16_SLICES, (long)HW / 64));
-    if (CH <= 256 && 256 % CH == 0)
+    const bool rows = CH <= 256 && 256 % CH == 0;
+    if (rows)
         hipLaunchKernelGGL(gn_stats_rows_bf16_kernel, dim3(S, B), dim3(256), 0, stream, (const bf16_t*)x, partial_ws, HW, C, groups, S);
     else
         hipLaunchKernelGGL(gn_stats_bf16_kernel, dim3(S, groups, B), dim3(256), 0, stream, (const bf16_t*)x, partial_ws, HW, C, groups, S);
-    hipLaunchKernelGGL(gn_finalize_bf16_kernel, dim3(B * groups), dim3(64), 0, stream, (const bf16_t*)x, partial_ws, stats, HW, C, groups, eps,
-                       B * groups, S);
+    hipLaunchKernelGGL(gn_finalize_bf16_kernel, dim3(B * groups), dim3(64), 0, stream, partial_ws, stats, rows ? (long)HW : (long)HW * (C / groups),
+                       rows ? C / groups : 1, eps, S);
     hipLaunchKernelGGL(gn_affine_kernel, dim3(ceil_div(B * C, 256)), dim3(256), 0, stream, stats, gamma, beta, ab, C, groups, B * C);
     const long total8 = (long)HW * C / 8;
     const int blocks = (int)min((long)ceil_div(total8, 256), 4096L);

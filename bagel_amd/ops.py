@@ -1261,7 +1261,7 @@ def conv_gemm_bf16(x, ld_in, w, ld_w, bias, residual, out, ld_out, B, Hin, Win, 
 
 
 def groupnorm_bf16_workspace_floats(B, C, groups):
-    """[B * groups][1024 slices][2] partial sums + (mean, rstd) per group + (scale, shift) per channel (include/bagel_hip.h)."""
+    """[B * groups][1024 slices][2] slice moments (mean, M2) + (mean, rstd) per group + (scale, shift) per channel (include/bagel_hip.h)."""
     return B * groups * 2050 + B * C * 2
 
 

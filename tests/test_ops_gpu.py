@@ -568,20 +568,40 @@ def test_conv1x1_and_nt_gemm():
     close32(eng.gemm_nt(a.to(DEV), b.to(DEV)), a @ b.t(), what="nt gemm")
 
 
-@pytest.mark.parametrize("C,swish", [(32, True), (64, False), (128, True)])
-def test_groupnorm_swish(C, swish):
+@pytest.mark.parametrize("C,swish,kind", [(32, True, "benign"), (64, False, "benign"), (128, True, "benign"), (64, False, "pivot0")],
+                         ids=["32-True", "64-False", "128-True", "64-False-pivot0"])
+def test_groupnorm_swish(C, swish, kind):
     eng, _ = _vae_engine()
     from torch import nn
     g = torch.Generator().manual_seed(3)
-    x = torch.randn(2, C, 12, 20, generator=g) * 3 + 5.0     # large mean: the shifted accumulation must not cancel
+    if kind == "benign":
+        x = torch.randn(2, C, 12, 20, generator=g) * 3 + 5.0     # large mean: the accumulation must not cancel
+    else:
+        # N(0, 0.05^2) with the FIRST element of every group (pixel 0, its first channel) at 200, 37 x 173 pixels: statistics shifted by
+        # that element would lose eps * (200 / sigma)^2 of rstd
+        x = torch.randn(2, C, 37, 173, generator=g) * 0.05
+        x[:, ::C // 32, 0, 0] = 200.0
     m = nn.Module()
     m.weight = nn.Parameter(1 + 0.1 * torch.randn(C, generator=g))
     m.bias = nn.Parameter(0.1 * torch.randn(C, generator=g))
-    ref = F.group_norm(x, 32, m.weight, m.bias, 1e-6)
+    if kind == "benign":
+        ref = F.group_norm(x, 32, m.weight, m.bias, 1e-6)
+    else:
+        ref = F.group_norm(x.double(), 32, m.weight.double(), m.bias.double(), 1e-6)
     if swish:
         ref = ref * torch.sigmoid(ref)
     out = eng.gn(x.permute(0, 2, 3, 1).contiguous().to(DEV), m.to(DEV), swish)
+    if kind != "benign":
+        B, G = 2, 32
+        stats = eng._ws[B * G * 64 * 2:B * G * (64 * 2 + 2)].cpu().view(B, G, 2)
+        rstd = (x.double().view(B, G, -1).var(-1, unbiased=False) + 1e-6).rsqrt()
+        print(f"groupnorm fp32 pivot outlier: rstd relative error {((stats[..., 1].double() - rstd).abs() / rstd).max().item():.3g}")
     close32(out.permute(0, 3, 1, 2), ref, tol=3e-5, what="groupnorm")
+    if kind != "benign":
+        # the 64 outliers come out near 113 and set the scale of the check above; the other elements are held to the same 3e-5 of THEIR
+        # largest value (a fp32 result with honest statistics is within 1e-6 of it)
+        rest = x != 200.0
+        close32(out.permute(0, 3, 1, 2).cpu()[rest], ref[rest], tol=3e-5, what="groupnorm, all but the outliers")
 
 
 def test_softmax_rows():
