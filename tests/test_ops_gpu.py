@@ -280,6 +280,45 @@ def test_qknorm_rope(hd, dp, nq, nkv, gen):
 # ------------------------------------------------------------------------------------------------------------
 # attention
 # ------------------------------------------------------------------------------------------------------------
+def attention_device_inputs(q, k, v, kc, vc, q_lens, ctx_lens, nq, nkv, D, pad_rows=0):
+    """The device layout ``attn_varlen`` reads, from host q [M, nq, D], new k / v [M, nkv, D] and context k / v [>= Ctot, nkv, D]: fused
+    [q|k|v] rows (+ ``pad_rows`` zero rows no range covers), V^T images with every sample on its own 64-column blocks, the context triple
+    as ``kwargs`` (empty without a context)."""
+    B = len(q_lens)
+    M, Ctot = sum(q_lens), sum(ctx_lens)
+    o = ops()
+    qkv = torch.cat([q.reshape(M, -1), k.reshape(M, -1), v.reshape(M, -1)], 1)
+    if pad_rows:
+        qkv = torch.cat([qkv, torch.zeros(pad_rows, qkv.shape[1], dtype=BF16)])
+    qkv = qkv.to(DEV)
+    qw, kw = nq * D, nkv * D
+    i32 = lambda x: torch.tensor(x, dtype=torch.int32, device=DEV)  # noqa: E731
+    cu_q = [0]
+    for n in q_lens:
+        cu_q.append(cu_q[-1] + n)
+
+    def cols(lens):
+        out, c = [], 0
+        for n in lens:
+            out.append(c)
+            c += (max(n, 1) + 63) // 64 * 64
+        return out, c
+    vcol, vtot = cols(q_lens)
+    vt = torch.zeros((kw, (vtot + 255) // 256 * 256), dtype=BF16, device=DEV)
+    o.v_transpose(qkv[:, qw + kw:], vt, i32(cu_q), i32(vcol), B, max(q_lens), nkv, D)
+    kwargs, cu_c, ccol, vtc = {}, None, None, None
+    if Ctot > 0:
+        cu_c = [0]
+        for n in ctx_lens:
+            cu_c.append(cu_c[-1] + n)
+        ccol, ctot = cols(ctx_lens)
+        vtc = torch.zeros((kw, (ctot + 255) // 256 * 256), dtype=BF16, device=DEV)
+        vcd = vc.reshape(vc.shape[0], -1)[:Ctot].to(DEV)
+        o.v_transpose(vcd, vtc, i32(cu_c), i32(ccol), B, max(ctx_lens), nkv, D)
+        kwargs = dict(k_ctx=kc.reshape(kc.shape[0], -1)[:Ctot].to(DEV), vt_ctx=vtc, cu_ctx=i32(cu_c), vt_ctx_col=i32(ccol))
+    return dict(qkv=qkv, vt=vt, vtc=vtc, cu_q=cu_q, vcol=vcol, cu_c=cu_c, ccol=ccol, kwargs=kwargs, i32=i32)
+
+
 def run_attention(q_lens, ctx_lens, nq, nkv, D, causal, seed=0, scale_dim=None, planned=None):
     """Builds packed q/k/v (+context), runs v_transpose + attn_varlen, returns (got, ref).
     ``planned`` = dict(n_workers=, split_min_tiles=): also run the persistent planned kernel on the same device tensors and return
@@ -305,29 +344,10 @@ def run_attention(q_lens, ctx_lens, nq, nkv, D, causal, seed=0, scale_dim=None, 
                       max(q_lens), 0, softmax_scale=scale, causal=causal)
     # device side: fused [q|k|v] rows like the layer loop produces
     o = ops()
-    qkv = torch.cat([q.reshape(M, -1), k.reshape(M, -1), v.reshape(M, -1)], 1).to(DEV)
+    dv = attention_device_inputs(q, k, v, kc, vc, q_lens, ctx_lens, nq, nkv, D)
+    qkv, vt, vcol, kwargs, cu_c, ccol = dv["qkv"], dv["vt"], dv["vcol"], dv["kwargs"], dv["cu_c"], dv["ccol"]
     qw, kw = nq * D, nkv * D
-    i32 = lambda x: torch.tensor(x, dtype=torch.int32, device=DEV)  # noqa: E731
-
-    def cols(lens):
-        out, c = [], 0
-        for n in lens:
-            out.append(c)
-            c += (max(n, 1) + 63) // 64 * 64
-        return out, c
-    vcol, vtot = cols(q_lens)
-    vt = torch.zeros((kw, (vtot + 255) // 256 * 256), dtype=BF16, device=DEV)
-    o.v_transpose(qkv[:, qw + kw:], vt, i32(cu_q), i32(vcol), B, max(q_lens), nkv, D)
-    kwargs = {}
-    if Ctot > 0:
-        cu_c = [0]
-        for n in ctx_lens:
-            cu_c.append(cu_c[-1] + n)
-        ccol, ctot = cols(ctx_lens)
-        vtc = torch.zeros((kw, (ctot + 255) // 256 * 256), dtype=BF16, device=DEV)
-        vcd = vc.reshape(Ctot, -1).to(DEV)
-        o.v_transpose(vcd, vtc, i32(cu_c), i32(ccol), B, max(ctx_lens), nkv, D)
-        kwargs = dict(k_ctx=kc.reshape(Ctot, -1).to(DEV), vt_ctx=vtc, cu_ctx=i32(cu_c), vt_ctx_col=i32(ccol))
+    i32 = dv["i32"]
     out = torch.full((M, qw), float("nan"), dtype=BF16, device=DEV)
     o.attn_varlen(qkv[:, :qw], qkv[:, qw:qw + kw], vt, out, i32(cu_q), i32(vcol), B, max(q_lens), nq, nkv, D, causal, scale, **kwargs)
     if planned is None:
