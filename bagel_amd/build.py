@@ -1,4 +1,4 @@
-"""Build libbagel_hip.so (gfx950) in-tree with hipcc.  No torch headers, no cmake: one .o per .hip, one link.
+"""Build libbagel_hip.so (gfx950) in-tree with hipcc.  No torch headers, no cmake: one .o per source, one link.
 
     python -m bagel_amd.build [--force] [--keep-temps]
 
@@ -28,7 +28,12 @@ def _hipcc():
 
 
 def sources():
-    return sorted(f for f in os.listdir(CSRC) if f.endswith(".hip"))
+    """The .hip units and the host-only .cpp (host_plan.cpp: compiled as plain C++ -- hipcc would take a .cpp for HIP -- so it carries no device code)."""
+    return sorted(f for f in os.listdir(CSRC) if f.endswith((".hip", ".cpp")))
+
+
+def _obj(s):
+    return os.path.join(OBJ, os.path.splitext(s)[0] + ".o")
 
 
 def _digest(paths):
@@ -61,7 +66,7 @@ def build(force=False, keep_temps=False, verbose=True):
     headers = [os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith(".h")] + [os.path.join(os.path.dirname(HERE), "include", "bagel_hip.h")]
     manifest = _load_manifest()
     digests = {s: _digest([os.path.join(CSRC, s)] + headers) for s in sources()}       # (common.h includes the public header: it is an input of every object)
-    todo = [s for s in sources() if force or manifest.get(s) != digests[s] or not os.path.exists(os.path.join(OBJ, s[:-4] + ".o"))]
+    todo = [s for s in sources() if force or manifest.get(s) != digests[s] or not os.path.exists(_obj(s))]
     if not todo and os.path.exists(LIB) and manifest.get("__lib__") == sorted(digests.values()):
         return LIB                                     # everything up to date (by content)
     try:
@@ -73,8 +78,10 @@ def build(force=False, keep_temps=False, verbose=True):
     jobs = []
     for s in todo:
         src = os.path.join(CSRC, s)
-        obj = os.path.join(OBJ, s[:-4] + ".o")
-        cmd = [hipcc] + FLAGS + ["-c", src, "-o", obj]
+        if s.endswith(".cpp"):
+            cmd = [hipcc] + [f for f in FLAGS if not f.startswith("--offload-arch")] + ["-x", "c++", "-c", src, "-o", _obj(s)]
+        else:
+            cmd = [hipcc] + FLAGS + ["-c", src, "-o", _obj(s)]
         if keep_temps:
             cmd.append("-save-temps=obj")
         jobs.append((s, cmd))
@@ -90,7 +97,7 @@ def build(force=False, keep_temps=False, verbose=True):
                     raise RuntimeError(f"hipcc failed on {name}")
                 if verbose:
                     print(f"[bagel_amd.build] compiled {name}")
-    objs = [os.path.join(OBJ, s[:-4] + ".o") for s in sources()]
+    objs = [_obj(s) for s in sources()]
     r = subprocess.run([hipcc, "-shared", "-fPIC", f"--offload-arch={ARCH}", "-o", LIB] + objs, capture_output=True, text=True)
     if r.returncode != 0:
         sys.stderr.write(r.stdout + r.stderr)

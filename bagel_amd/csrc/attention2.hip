@@ -30,31 +30,7 @@
 #include <type_traits>
 #include <vector>
 
-struct AttnItem {        // 16 ints = 64 bytes, written by the host planner
-    int q_row0;          // absolute row (q / out buffers) of the item's first query row
-    int nrows;           // live query rows: <= 256 (head-per-wave form: <= 32)
-    int h;               // query head (head-per-wave: first head of the KV group)
-    int g;               // KV head
-    int flags;           // bit 0 head-per-wave, bit 1 causal, bit 2 partial output; bits 8..15 = G (waves that are live in head-per-wave form)
-    int q_rel0;          // index of the first query row inside its sample's new segment (causal mask)
-    int kn_row0;         // absolute row of new-segment key 0 in k_new
-    int l_new;           // keys in the sample's new segment
-    int kc_row0;         // absolute row of context key 0 in k_ctx
-    int l_ctx;           // context keys
-    int vtn_col0;        // V^T column of new-segment key 0
-    int vtc_col0;        // V^T column of context key 0
-    int t0, t1;          // 64-key tile range [t0, t1) over the sample's tile list [context tiles | new tiles]
-    int part;            // partial slot (flags bit 2)
-    int pad;
-};
-#define ATTN2_HPW 1
-#define ATTN2_CAUSAL 2
-#define ATTN2_PARTIAL 4
-
-struct AttnComb {        // 8 ints: one key-split item = `nslots` consecutive partial slots -> one output tile
-    int q_row0, nrows, h, flags, slot0, nslots, pad0, pad1;
-};
-
+// AttnItem / AttnComb / ATTN2_*: host_plan.h (the planner that writes them is host_plan.cpp)
 struct Attn2Params {
     const bf16_t* q; long ldq;
     const bf16_t* k_new; long ldk_new;
@@ -647,163 +623,6 @@ __global__ __launch_bounds__(256) void attn2_combine_kernel(const AttnComb* __re
     }
 }
 
-// ---------------------------------------------------------------------------------------------------------
-// Host planner (no device code).  Layout of the plan buffer (int32):
-//   [0] n_workers  [1] n_items  [2] n_comb  [3] n_slots  [4] offset of the item table  [5] offset of the combine table
-//   [6] makespan (tile steps of the busiest worker)  [7] total tile steps
-//   [8 .. 8 + n_workers]  worker_off      then (16-int aligned) items[n_items][16], comb[n_comb][8]
-// Worker w is assumed to run on XCD w % 8 (the hardware deals workgroup ids round-robin; an assumption for speed only).
-// ---------------------------------------------------------------------------------------------------------
-namespace {
-struct PItem { AttnItem it; int cost; };
-inline int cdiv(int a, int b) { return (a + b - 1) / b; }
-}
-
-extern "C" int bagel_attn_plan(const int32_t* q_start, const int32_t* q_len, const int32_t* ctx_start, const int32_t* ctx_len,
-                               const int32_t* vt_new_col, const int32_t* vt_ctx_col, int32_t batch, int32_t nq, int32_t nkv,
-                               int32_t causal, int32_t n_workers, int32_t split_min_tiles, int32_t* plan, int64_t plan_ints) {
-    BAGEL_REQUIRE(q_start && q_len && vt_new_col && plan, "attn_plan: null pointer");
-    BAGEL_REQUIRE(nq > 0 && nkv > 0 && nq % nkv == 0, "attn_plan: bad head counts %d/%d", nq, nkv);
-    BAGEL_REQUIRE(n_workers > 0 && n_workers % 8 == 0, "attn_plan: the worker count must be a multiple of the 8 XCDs");
-    const int G = nq / nkv, wpx = n_workers / 8;
-    if (split_min_tiles <= 0) split_min_tiles = 16;
-    // ---- items of every (sample, KV head) pair, query tiles ascending ----
-    std::vector<std::vector<PItem>> pairs;
-    for (int b = 0; b < batch; ++b) {
-        const int Lq = q_len[b], C = ctx_len ? ctx_len[b] : 0;
-        if (Lq <= 0) continue;
-        const int nt_ctx = cdiv(C, 64);
-        const int nqt = cdiv(Lq, 256);
-        for (int g = 0; g < nkv; ++g) {
-            std::vector<PItem> v;
-            for (int qt = 0; qt < nqt; ++qt) {
-                const int nrows = std::min(256, Lq - 256 * qt);
-                const int vis = causal ? std::min(Lq, 256 * qt + nrows) : Lq;        // new-segment keys any row of the tile may see
-                const int T = nt_ctx + cdiv(vis, 64);
-                const bool hpw = nrows <= 32 && G <= 8 && G > 1;
-                AttnItem it = {};
-                it.q_row0 = q_start[b] + 256 * qt; it.nrows = nrows; it.g = g;
-                it.flags = (hpw ? ATTN2_HPW : 0) | (causal ? ATTN2_CAUSAL : 0) | (G << 8);
-                it.q_rel0 = 256 * qt; it.kn_row0 = q_start[b]; it.l_new = Lq;
-                it.kc_row0 = (C > 0 && ctx_start) ? ctx_start[b] : 0; it.l_ctx = C;
-                it.vtn_col0 = vt_new_col[b]; it.vtc_col0 = (C > 0 && vt_ctx_col) ? vt_ctx_col[b] : 0;
-                it.t0 = 0; it.t1 = T; it.part = -1;
-                if (hpw) { it.h = g * G; v.push_back({it, T}); }
-                else for (int j = 0; j < G; ++j) { it.h = g * G + j; v.push_back({it, T}); }
-            }
-            pairs.push_back(std::move(v));
-        }
-    }
-    // ---- virtual pairs: when the pairs do not fill the 8 XCDs evenly, every pair is dealt into interleaved sets of items ----
-    const int npairs = (int)pairs.size();
-    std::vector<std::vector<PItem>> vps;
-    if (npairs > 0) {
-        int gcd8 = 8;
-        while (npairs % gcd8) gcd8 >>= 1;
-        const int qsplit = 8 / gcd8;
-        for (auto& pr : pairs)
-            for (int s = 0; s < qsplit; ++s) {
-                std::vector<PItem> v;
-                for (size_t j = s; j < pr.size(); j += qsplit) v.push_back(pr[j]);
-                if (!v.empty()) vps.push_back(std::move(v));
-            }
-    }
-    // ---- virtual pairs -> XCDs: heaviest first onto the least loaded XCD ----
-    std::vector<long> vcost(vps.size(), 0);
-    for (size_t i = 0; i < vps.size(); ++i) for (auto& x : vps[i]) vcost[i] += x.cost;
-    std::vector<int> order(vps.size());
-    for (size_t i = 0; i < order.size(); ++i) order[i] = (int)i;
-    std::stable_sort(order.begin(), order.end(), [&](int a, int b2) { return vcost[a] > vcost[b2]; });
-    std::vector<std::vector<int>> xcd_vps(8);
-    long xload[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-    for (int i : order) {
-        int best = 0;
-        for (int x = 1; x < 8; ++x) if (xload[x] < xload[best]) best = x;
-        xcd_vps[best].push_back(i);
-        xload[best] += vcost[i];
-    }
-    // ---- inside an XCD: longest-processing-time dealing of its item stream (virtual pair after virtual pair, heavy items first inside
-    //      one) onto its `wpx` workers -- every item goes to the least loaded worker, which for equal costs is plain round-robin: the 32
-    //      workers then sit on the same (sample, KV head) pair at the same time.  An item that would push its worker more than `slack`
-    //      tile steps past the XCD's mean load is held back; the held-back items are cut along the key axis into contiguous tile ranges
-    //      that fill the workers up to the mean (stream-K over the leftovers, chunks of >= min_chunk tiles), each range a sub-item
-    //      that writes partials. ----
-    std::vector<std::vector<AttnItem>> wl(n_workers);
-    std::vector<long> wload(n_workers, 0);
-    std::vector<AttnComb> combs;
-    int n_slots = 0;
-    const int min_chunk = std::max(split_min_tiles / 2, 1);
-    for (int x = 0; x < 8; ++x) {
-        std::vector<PItem> stream;
-        for (int i : xcd_vps[x]) {
-            std::vector<PItem> v = vps[i];
-            std::stable_sort(v.begin(), v.end(), [](const PItem& a, const PItem& b2) { return a.cost > b2.cost; });
-            stream.insert(stream.end(), v.begin(), v.end());
-        }
-        if (stream.empty()) continue;
-        long tot = 0;
-        for (auto& pi : stream) tot += pi.cost;
-        const long mean = (tot + wpx - 1) / wpx;
-        const long slack = 2;
-        auto least = [&]() { int best = x; for (int j = 1; j < wpx; ++j) if (wload[j * 8 + x] < wload[best]) best = j * 8 + x; return best; };
-        std::vector<PItem> held;
-        for (auto& pi : stream) {
-            const int w = least();
-            const bool splittable = pi.cost >= split_min_tiles && pi.cost >= 2 * min_chunk;
-            if (wload[w] + pi.cost > mean + slack && splittable) { held.push_back(pi); continue; }
-            wl[w].push_back(pi.it);
-            wload[w] += pi.cost;
-        }
-        // the held-back items as one stream of tiles: every cut gives the currently least loaded worker what it lacks to the mean
-        for (auto& pi : held) {
-            const int T = pi.it.t1 - pi.it.t0;
-            std::vector<std::pair<int, int>> cuts;      // (worker, tiles)
-            int left = T;
-            while (left > 0) {
-                const int w = least();
-                long want = mean - wload[w];
-                if (want < min_chunk) want = min_chunk;
-                int n = (int)std::min<long>(want, left);
-                if (left - n < min_chunk) n = left;                     // no crumbs
-                cuts.push_back({w, n});
-                wload[w] += n;
-                left -= n;
-            }
-            if (cuts.size() == 1) { wl[cuts[0].first].push_back(pi.it); continue; }
-            AttnComb c = {pi.it.q_row0, pi.it.nrows, pi.it.h, pi.it.flags, n_slots, (int)cuts.size(), 0, 0};
-            combs.push_back(c);
-            int at = pi.it.t0;
-            for (auto& cw : cuts) {
-                AttnItem sub = pi.it;
-                sub.t0 = at; sub.t1 = at + cw.second; at += cw.second;
-                sub.flags |= ATTN2_PARTIAL;
-                sub.part = n_slots++;
-                wl[cw.first].push_back(sub);
-            }
-        }
-    }
-    int n_items = 0;
-    long total = 0, makespan = 0;
-    for (int w = 0; w < n_workers; ++w) { n_items += (int)wl[w].size(); total += wload[w]; makespan = std::max(makespan, wload[w]); }
-    const int off_items = ((8 + n_workers + 1) + 15) / 16 * 16;
-    const int off_comb = off_items + 16 * n_items;
-    const long need = (long)off_comb + 8L * (long)combs.size();
-    BAGEL_REQUIRE(need <= plan_ints, "attn_plan: the plan needs %ld ints, the buffer holds %ld", need, (long)plan_ints);
-    plan[0] = n_workers; plan[1] = n_items; plan[2] = (int)combs.size(); plan[3] = n_slots; plan[4] = off_items; plan[5] = off_comb;
-    plan[6] = (int)makespan; plan[7] = (int)std::min<long>(total, 0x7fffffff);
-    int at = 0;
-    AttnItem* items = (AttnItem*)(plan + off_items);
-    for (int w = 0; w < n_workers; ++w) {
-        plan[8 + w] = at;
-        for (auto& it : wl[w]) items[at++] = it;
-    }
-    plan[8 + n_workers] = at;
-    for (int i = 8 + n_workers + 1; i < off_items; ++i) plan[i] = 0;
-    AttnComb* cb = (AttnComb*)(plan + off_comb);
-    for (size_t i = 0; i < combs.size(); ++i) cb[i] = combs[i];
-    return BAGEL_OK;
-}
-
 extern "C" int bagel_attn_planned_bf16(const void* q, int64_t ldq, const void* k_new, int64_t ldk_new, const void* vt_new,
                                        int64_t ldvt_new, const void* k_ctx, int64_t ldk_ctx, const void* vt_ctx, int64_t ldvt_ctx,
                                        void* out, int64_t ldo, const int32_t* plan_dev, int32_t n_workers, int32_t n_comb,
@@ -828,15 +647,8 @@ extern "C" int bagel_attn_planned_bf16(const void* q, int64_t ldq, const void* k
     p.scale_log2 = softmax_scale * 1.4426950408889634f;
     const dim3 grid(n_workers), block(512);
     // a plan with MORE workers than the device has CUs asks for two resident workgroups per CU: the split-ring kernel (64 KB of LDS per workgroup)
-    static int cus_of[64] = {0};
-    int dev = 0, cus = 0;
-    if (hipGetDevice(&dev) != hipSuccess) return bagel_set_error(BAGEL_ERR_LAUNCH, "attn_planned: cannot query the device");
-    if (dev >= 0 && dev < 64 && cus_of[dev] > 0) cus = cus_of[dev];
-    else {
-        if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus <= 0)
-            return bagel_set_error(BAGEL_ERR_LAUNCH, "attn_planned: cannot query the device");
-        if (dev >= 0 && dev < 64) cus_of[dev] = cus;
-    }
+    int cus = 0;
+    if (int rc = bagel_device_cus(&cus)) return rc;
     const bool split = n_workers > cus;
     if (head_dim == 128) {
         constexpr int smem = A2_SLOTS * (64 * 256 + 128 * 128), smem_split = 2 * (64 * 256 + 128 * 128);

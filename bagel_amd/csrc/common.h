@@ -2,9 +2,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
-// the public C ABI: every translation unit sees the prototypes of the entry points it defines, so a definition that drifts from include/bagel_hip.h is a
-// COMPILE error ("conflicting types") instead of a ctypes call with the wrong arguments at run time
-#include "../../include/bagel_hip.h"
+#include "host_plan.h"   // the public C ABI, the error convention (BAGEL_OK / BAGEL_ERR_* / bagel_set_error / BAGEL_REQUIRE) and the host-side planners
 
 typedef unsigned short bf16_t;   // raw bf16 bits
 typedef __attribute__((ext_vector_type(8))) short bf16x8_t;   // MFMA A/B fragment (8 bf16 = 4 VGPR)
@@ -13,21 +11,13 @@ typedef __attribute__((ext_vector_type(16))) float f32x16_t;
 typedef __attribute__((ext_vector_type(4))) unsigned int u32x4_t;
 typedef __attribute__((ext_vector_type(2))) unsigned int u32x2_t;
 
-#define BAGEL_OK 0
-#define BAGEL_ERR_ARG (-1)
-#define BAGEL_ERR_LAUNCH (-2)
-#define BAGEL_ERR_UNSUPPORTED (-3)
-
-int bagel_set_error(int code, const char* fmt, ...);
 int bagel_check_launch(const char* what);
 // hipFuncSetAttribute(MaxDynamicSharedMemorySize) once per (kernel, device): a process that drives several GPUs must enable
 // the > 64 KB LDS kernels on each of them; the return code is checked and reported through bagel_set_error.
 int bagel_enable_lds(const void* func, int bytes, const char* what);
 
-#define BAGEL_REQUIRE(cond, ...)                                  \
-    do {                                                          \
-        if (!(cond)) return bagel_set_error(BAGEL_ERR_ARG, __VA_ARGS__); \
-    } while (0)
+// multiprocessor count of the current device, cached per device id (a process may drive several, and a CU-masked device reports its own count)
+int bagel_device_cus(int* cus);
 
 // ---- bf16 <-> f32 (round-to-nearest-even, identical to torch's CPU/GPU conversion) ----
 __device__ __forceinline__ float bf2f(bf16_t v) { return __uint_as_float(((unsigned)v) << 16); }

@@ -36,12 +36,8 @@
 #define EPI_SILU 2
 #define EPI_SWIGLU16 3
 
-#define ENG_MAXPH 4
-#define ENG_MAX_SLOTS 8
-#define ENG_MAX_DPAIRS 32                 // split-K pairs one workgroup may own (partials live in LDS)
-#define ENG_SYNC_BYTES 2560
+// ENG_MAXPH / ENG_MAX_SLOTS / ENG_MAX_DPAIRS / ENG_SYNC_BYTES / ENG_LDS_MAX: host_plan.h (eng_geometry sizes the LDS ring with them)
 #define ENG_RB_PAIRS 64                   // row pairs per workgroup whose bias / residual dwords are staged in LDS at the hand-off
-#define ENG_LDS_MAX (160 * 1024)
 #define ENG_SPIN_LDS (1u << 23)           // bound of an LDS poll loop (~1 s)
 #define ENG_SPIN_GLOBAL (1u << 19)        // bound of a flag sweep loop (~1-2 s)
 
@@ -658,17 +654,8 @@ static int eng_env(const char* name, int dflt) {
 }
 
 extern "C" int bagel_decode_engine_workgroups(void) {
-    // per device (a process may drive several, and a CU-masked device reports its own count); a racing first call computes the same value twice
-    static int n_of[64] = {0};
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess)
-        return bagel_set_error(BAGEL_ERR_LAUNCH, "decode_engine: cannot query the device");
-    const bool cached = dev >= 0 && dev < 64;
-    if (cached && n_of[dev] > 0) return n_of[dev];
     int n = 0;
-    if (hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n <= 0)
-        return bagel_set_error(BAGEL_ERR_LAUNCH, "decode_engine: cannot query the device");
-    if (cached) n_of[dev] = n;
+    if (int rc = bagel_device_cus(&n)) return rc;
     return n;
 }
 
@@ -677,6 +664,18 @@ extern "C" int bagel_decode_engine_sync_bytes(int32_t n_phases) {
     if (n_wg <= 0) return n_wg;
     if (n_phases <= 0) return 0;
     return (n_phases * n_wg * 4 + 255) / 256 * 256;
+}
+
+// validation + geometry of a chain on the current device (host_plan.cpp), with the BAGEL_ENGINE_* knobs
+static int eng_plan(const void* const* ptrs, const int64_t* dims, int32_t n_phases, EngGeometry* g) {
+    const int n_wg = bagel_decode_engine_workgroups();
+    if (n_wg <= 0) return n_wg;
+    return eng_geometry(ptrs, dims, n_phases, n_wg, eng_env("BAGEL_ENGINE_SLOTS", ENG_MAX_SLOTS), eng_env("BAGEL_ENGINE_WAVES", 8),
+                        eng_env("BAGEL_ENGINE_LOADERS", 2), eng_env("BAGEL_ENGINE_DEPTH", 2), g);
+}
+extern "C" int bagel_decode_engine_check(const void* const* ptrs, const int64_t* dims, int32_t n_phases) {
+    EngGeometry g;
+    return eng_plan(ptrs, dims, n_phases, &g);
 }
 
 static int eng_launch(const void* const* ptrs, const int64_t* dims, int32_t n_phases, float eps, void* sync_ws, void* status, void* trace,
@@ -692,17 +691,15 @@ extern "C" int bagel_decode_engine_traced_bf16(const void* const* ptrs, const in
 }
 static int eng_launch(const void* const* ptrs, const int64_t* dims, int32_t n_phases, float eps, void* sync_ws, void* status, void* trace,
                       hipStream_t stream) {
-    BAGEL_REQUIRE(ptrs && dims && sync_ws && status, "decode_engine: null pointer");
-    BAGEL_REQUIRE(n_phases >= 1 && n_phases <= ENG_MAXPH, "decode_engine: 1..%d phases (got %d)", ENG_MAXPH, n_phases);
-    const int n_wg = bagel_decode_engine_workgroups();
-    if (n_wg <= 0) return n_wg;
+    BAGEL_REQUIRE(sync_ws && status, "decode_engine: null pointer");
+    EngGeometry g;
+    if (int rc = eng_plan(ptrs, dims, n_phases, &g)) return rc;
     EngParams p;
     p.nph = n_phases;
     p.eps = eps;
     p.flags = (unsigned*)sync_ws;
     p.status = (unsigned*)status;
     p.trace = (unsigned long long*)trace;
-    int max_k = 0, slot = 0;
     for (int i = 0; i < n_phases; ++i) {
         EngPhase& P = p.ph[i];
         const void* const* q = ptrs + 6 * i;
@@ -710,58 +707,15 @@ static int eng_launch(const void* const* ptrs, const int64_t* dims, int32_t n_ph
         P.A = (const bf16_t*)q[0]; P.W = (const bf16_t*)q[1]; P.bias = (const bf16_t*)q[2]; P.norm_w = (const bf16_t*)q[3];
         P.R = (const bf16_t*)q[4]; P.C = (bf16_t*)q[5];
         P.N = (int)d[0]; P.K = (int)d[1]; P.ldw = d[2]; P.epi = (int)d[3];
-        BAGEL_REQUIRE(P.A && P.W && P.C, "decode_engine: phase %d: null A / W / C", i);
-        BAGEL_REQUIRE(P.K > 0 && (P.K % 8) == 0 && (P.ldw % 8) == 0, "decode_engine: phase %d: K / ldw must be multiples of 8", i);
-        BAGEL_REQUIRE(P.N > 0 && (P.N % 2) == 0, "decode_engine: phase %d: N = %d must be even", i, P.N);
-        BAGEL_REQUIRE(P.epi >= 0 && P.epi <= 3, "decode_engine: phase %d: unknown epilogue %d", i, P.epi);
-        BAGEL_REQUIRE(P.epi != EPI_SWIGLU16 || ((P.N % 32) == 0 && !P.bias && !P.R), "decode_engine: phase %d: swiglu needs N %% 32 == 0, no bias / residual", i);
-        BAGEL_REQUIRE((((uintptr_t)P.A | (uintptr_t)P.W | (uintptr_t)P.norm_w) & 15) == 0, "decode_engine: phase %d: A / W / norm_w must be 16-byte aligned", i);
-        BAGEL_REQUIRE((((uintptr_t)P.C | (uintptr_t)P.R) & 3) == 0, "decode_engine: phase %d: C / R must be 4-byte aligned", i);
-        BAGEL_REQUIRE(!P.norm_w || (P.K >> 3) <= 512, "decode_engine: phase %d: the fused RMSNorm serves K <= 4096", i);
-        BAGEL_REQUIRE(i == 0 || P.A == (const bf16_t*)p.ph[i - 1].C, "decode_engine: phase %d must read the previous phase's output", i);
-        BAGEL_REQUIRE(i == 0 || P.K == (p.ph[i - 1].epi == EPI_SWIGLU16 ? p.ph[i - 1].N / 2 : p.ph[i - 1].N),
-                      "decode_engine: phase %d: K = %d does not match the previous phase's output length", i, P.K);
         P.in_launch = i > 0;
-        P.ngr = (P.K / 8 + 63) / 64;
-        // the split-K form of bagel_gemv_bf16 (launch_gemv_any): long un-normalised rows, few of them
-        P.kind = (!P.norm_w && P.K >= 8192 && P.N / 2 <= 8192) ? 2 : 0;
-        P.gq = (P.ngr + 3) / 4;
-        const int unit_groups = P.kind == 2 ? P.gq : P.ngr;
-        BAGEL_REQUIRE(2 * unit_groups <= 60, "decode_engine: phase %d: K = %d gives %d KB units (at most 60 LDS-DMA instructions in flight)", i, P.K, 2 * unit_groups);
-        if (P.kind == 2) {
-            const long max_pairs = ((long)P.N / 2 + n_wg - 1) / n_wg;
-            BAGEL_REQUIRE(max_pairs <= ENG_MAX_DPAIRS, "decode_engine: phase %d: %ld split-K pairs per workgroup (at most %d)", i, max_pairs, ENG_MAX_DPAIRS);
-        }
-        if (2 * unit_groups * 1024 > slot) slot = 2 * unit_groups * 1024;
-        if (P.K > max_k) max_k = P.K;
+        P.kind = g.kind[i]; P.ngr = g.ngr[i]; P.gq = g.gq[i];
     }
-    p.xs_bytes = (max_k * 2 + 1023) / 1024 * 1024;
-    p.slot_bytes = slot;
-    int nslot = (ENG_LDS_MAX - p.xs_bytes - ENG_SYNC_BYTES) / slot;
-    const int want = eng_env("BAGEL_ENGINE_SLOTS", ENG_MAX_SLOTS);
-    if (nslot > want) nslot = want;
-    if (nslot > ENG_MAX_SLOTS) nslot = ENG_MAX_SLOTS;
-    int waves = eng_env("BAGEL_ENGINE_WAVES", 8);
-    if (waves < 2) waves = 2;
-    if (waves > 8) waves = 8;
-    int nl = eng_env("BAGEL_ENGINE_LOADERS", 2);
-    if (nl < 1) nl = 1;
-    if (nl > 2) nl = 2;
-    if (nl >= waves) nl = waves - 1;
-    nslot -= nslot % nl;                                       // every loader owns the slots of its units
-    BAGEL_REQUIRE(nslot >= 2 * nl && nslot >= 3, "decode_engine: the LDS ring holds %d slots of %d bytes beside a %d-byte activation vector", nslot, slot, p.xs_bytes);
-    p.nslot = nslot;
-    p.nloaders = nl;
-    // units one loader keeps unpublished: fewer than its own slots, and `depth` of the largest unit must stay countable (<= 63 DMA instructions)
-    p.depth = eng_env("BAGEL_ENGINE_DEPTH", 2);
-    if (p.depth < 1) p.depth = 1;
-    if (p.depth > nslot / nl - 1) p.depth = nslot / nl - 1;
-    while (p.depth > 1 && p.depth * (slot / 1024) > 63) --p.depth;
+    p.xs_bytes = g.xs_bytes; p.slot_bytes = g.slot_bytes; p.nslot = g.nslot; p.nloaders = g.nloaders; p.depth = g.depth;
     p.nt = eng_env("BAGEL_ENGINE_NT", 1);
     p.abl = eng_env("BAGEL_ENGINE_ABL", 0);
-    const int smem = p.xs_bytes + nslot * slot + ENG_SYNC_BYTES;
+    const int smem = p.xs_bytes + p.nslot * p.slot_bytes + ENG_SYNC_BYTES;
     if (smem > 48 * 1024)
         if (int rc = bagel_enable_lds((const void*)decode_engine_kernel, ENG_LDS_MAX, "decode_engine_kernel")) return rc;
-    hipLaunchKernelGGL(decode_engine_kernel, dim3(n_wg), dim3(64 * waves), smem, stream, p);
+    hipLaunchKernelGGL(decode_engine_kernel, dim3(g.n_wg), dim3(64 * g.waves), smem, stream, p);
     return bagel_check_launch("decode_engine_kernel");
 }

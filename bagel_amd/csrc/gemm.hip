@@ -1238,52 +1238,12 @@ __global__ __launch_bounds__(512) void gemm_splitk_reduce_kernel(const GemmParam
         }
 }
 
-// How a tile count that leaves the last round of the persistent kernel nearly empty is scheduled (LLM prefill of the understanding
-// request: M = 4936 -> 20 row tiles; o / down have 280 tiles = 1.09 rounds of 256 CUs, qkv 360 = 1.41): the FULL rounds run as they
-// are, the leftover tiles are cut along K into `ksplit` parts each so that they fill the chip once more with work items 1 / ksplit as
-// long, and a small pass adds the parts up and applies the epilogue.  Returns the split (1 = do not split).
-static int pq_leftover_split(int nblk, int wgs, int nk, size_t ws_bytes, int* n_full_out) {
-    const int n_full = nblk / wgs * wgs, rest = nblk - n_full;
-    *n_full_out = n_full;
-    if (rest == 0) return 1;
-    // A/B knobs, READ ONCE PER PROCESS (C++11 thread-safe statics: host threads launching GEMMs concurrently do not race on them; a change of the
-    // environment after the first GEMM has no effect):
-    static const int policy = [] { const char* e = getenv("BAGEL_GEMM_SPLIT_POLICY"); return e ? atoi(e) : 0; }();   // 0 = the round-3 rule (fill the chip ONCE with the leftovers), 1 = the round-5 cost model
-    static const int force = [] { const char* f = getenv("BAGEL_GEMM_SPLIT_FORCE"); return f ? atoi(f) : 0; }();     // experiment: this many parts for every launch with leftovers
-    if (force > 1) {
-        int sf = force;
-        if (sf > nk / 4) sf = nk / 4;
-        while (sf > 1 && (size_t)rest * sf * (32 * 512 * 16) > ws_bytes) --sf;
-        return sf < 2 ? 1 : sf;
-    }
-    if (policy == 0) {
-        if (2 * rest > wgs + wgs / 4) return 1;                                // the last round is > 5/8 full anyway
-        if (n_full == 0 && (2 * rest > wgs || nk < 16)) return 1;              // a single round: split only when it fills less than half the chip
-        int s = wgs / rest;                                                    // parts per leftover tile: fill the chip once
-        if (s > nk / 4) s = nk / 4;                                            // a part keeps >= 4 k-tiles (prologue + steady state)
-        while (s > 1 && (size_t)rest * s * (32 * 512 * 16) > ws_bytes) --s;     // 256 KB of fp32 per part
-        return s < 2 ? 1 : s;
-    }
-    // Round 5: the parts of the leftover tiles may take SEVERAL passes over the chip (rest * s > wgs), priced with a small model calibrated on the bench's own
-    // launches: a 64-deep k-tile step of a 256 x 256 tile takes 1.52 us (gate+up at M = 32 768: 8.9 TFLOP in 6.32 ms = 4 144 steps), an item pays ~6 us of
-    // pipeline fill + epilogue, a part costs 512 KB of fp32 partial traffic (written here, read by the reduce pass: ~0.13 us when the chip shares it) and the
-    // reduce pass one more launch.  Un-split, the leftovers cost one whole tile time with (wgs - rest) CUs idle.  Example: the 3-stream edit forward has
-    // 672 o / down tiles = 2.63 rounds; o (K = 3 584) is left alone (a 3-way split costs 137 us against 90), down (K = 18 944) is cut three ways: two passes of
-    // third-length items = 380 us against 455.
-    const double t_step = 1.52, t_item = 6.0, t_part = 0.13, t_reduce = 6.0;
-    const double whole = nk * t_step + t_item;
-    if (n_full == 0 && nk < 16) return 1;
-    int best = 1;
-    double best_cost = whole * 0.85;                                           // a split has to win 15 % of the leftover round to be worth a second launch
-    for (int sp = 2; sp <= nk / 4 && sp <= 16; ++sp) {
-        if ((size_t)rest * sp * (32 * 512 * 16) > ws_bytes) break;
-        const int passes = (rest * sp + wgs - 1) / wgs;
-        const double cost = passes * ((double)nk / sp * t_step + t_item) + rest * sp * t_part + t_reduce;
-        // several passes (rest * sp > wgs) have to win a quarter of the round, not 15 %: measured on the edit request, the modelled 16 % of the three-way split of
-        // its `down` leftovers (160 tiles) came out as +1 % of the request (profiles/r05_gemm_split_policy.log)
-        if (cost < (passes > 1 ? whole * 0.75 : best_cost)) { best_cost = cost; best = sp; }
-    }
-    return best;
+// pq_leftover_split (host_plan.cpp) with its two A/B knobs, READ ONCE PER PROCESS (C++11 thread-safe statics: host threads launching GEMMs concurrently do not
+// race on them; a change of the environment after the first GEMM has no effect)
+static int pq_split(int nblk, int wgs, int nk, size_t ws_bytes, int* n_full_out) {
+    static const int policy = [] { const char* e = getenv("BAGEL_GEMM_SPLIT_POLICY"); return e ? atoi(e) : 0; }();
+    static const int force = [] { const char* f = getenv("BAGEL_GEMM_SPLIT_FORCE"); return f ? atoi(f) : 0; }();
+    return pq_leftover_split(nblk, wgs, nk, ws_bytes, policy, force, n_full_out);
 }
 
 template <int MODE, bool FP8 = false, bool SADDR = false, bool QOUT = false>
@@ -1297,22 +1257,16 @@ static int launch_gemm_pq(const GemmParams& p0, hipStream_t stream, void* ws = n
     p.tiles_m = t;
     p.tiles_n = ceil_div(p.N, 256);
     if (t == 0) return BAGEL_OK;
-    static int gm = 0, wgs_of_dev[16] = {0};   // read-once tuning knobs; the CU count is cached per device
+    static int gm = 0;                         // read-once tuning knob
     if (gm == 0) {
         const char* e = getenv("BAGEL_GEMM_GM");
         gm = (e && atoi(e) > 0) ? atoi(e) : 4;
     }
-    int dev = 0;
-    (void)hipGetDevice(&dev);
-    dev &= 15;
-    if (wgs_of_dev[dev] == 0) {
-        int cus = 0;
-        (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
-        const char* w = getenv("BAGEL_GEMM_PERSIST_WGS");
-        int v = (w && atoi(w) > 0) ? atoi(w) : cus;
-        wgs_of_dev[dev] = v < 8 ? 8 : (v & ~7);    // a multiple of 8 keeps every work item of a workgroup on its XCD
-    }
-    const int wgs = wgs_of_dev[dev];
+    static const int wgs_env = [] { const char* w = getenv("BAGEL_GEMM_PERSIST_WGS"); return (w && atoi(w) > 0) ? atoi(w) : 0; }();
+    int cus = 0;
+    (void)bagel_device_cus(&cus);
+    const int v = wgs_env ? wgs_env : cus;
+    const int wgs = v < 8 ? 8 : (v & ~7);      // a multiple of 8 keeps every work item of a workgroup on its XCD
     p.gm = gm;
     constexpr int smem = 2 * 4 * 128 * 128 + 3 * 2048;   // two k-tile stages + the three-deep row-table ring
     if (int rc = bagel_enable_lds((const void*)gemm_pq_kernel<MODE, FP8, SADDR, QOUT>, smem, "gemm_pq_kernel")) return rc;
@@ -1320,7 +1274,7 @@ static int launch_gemm_pq(const GemmParams& p0, hipStream_t stream, void* ws = n
     p.w_begin = 0; p.w_count = nblk; p.ksplit = 1; p.part = nullptr;
     if constexpr (!FP8 && MODE != 0) {
         int n_full = 0;
-        const int s = ws ? pq_leftover_split(nblk, wgs, p.K >> 6, ws_bytes, &n_full) : 1;
+        const int s = ws ? pq_split(nblk, wgs, p.K >> 6, ws_bytes, &n_full) : 1;
         if (s > 1) {
             // (1) the full rounds, one pass; (2) the leftover tiles as K parts -> fp32 partials; (3) sum + epilogue
             if (n_full > 0) {

@@ -289,80 +289,16 @@ __global__ __launch_bounds__(256) void gemv_mb_reduce_kernel(const MbParams p) {
     mb_epilogue(p, a, m, n);
 }
 
-// Geometry.  Instantiations: NS = 4 (short rows, K <= 1024: the tiny test models), 10, 14 (K = 3584 in one slice: 14 steps per wave at the 7B
-// hidden size), 19.  The launch is PERSISTENT: one workgroup per CU (its ~170 registers x 8 waves leave no room for a second one), each
-// taking an even share of the column blocks of its K slice, so the activation prologue is paid once per workgroup and launch.
-// Rows too long for one slice (nsteps > 8 x 19) are cut over KS workgroups; KS and the workgroups per slice are chosen together so that
-// the blocks divide evenly and the whole chip is used: the 7B down projection (592 steps, 224 blocks, 256 CUs) runs as 8 slices x 32
-// workgroups x 7 blocks x 10 steps per wave -- 4 slices x 64 workgroups would leave 3 or 4 blocks per workgroup (makespan 4 of 3.5).
-// BAGEL_MB_WGS overrides the workgroup count (tuning / tests).
-static const int MB_NS[] = {4, 10, 14, 19};
-
-// Two request blocks (17..32 rows) keep 2 x NS activation fragments per wave: NS = 19 does not fit the register file beside them, so the longest
-// one-slice row is 8 x 14 steps (K = 3584, the 7B hidden size) and longer rows take more, shorter slices.
-static int mb_max_ns(int MB) { return MB > 1 ? 14 : 19; }
-
-static int mb_ns_for(int per, int MB = 1) {
-    for (int ns : MB_NS)
-        if (per <= ns && ns <= mb_max_ns(MB)) return ns;
-    return 0;
-}
-
-static void mb_geometry(int N, int K, int wgs, int MB, int* per, int* KS, int* gx_out) {
-    const int nsteps = K / 32, nblk = N / 16;
-    const int NSM = mb_max_ns(MB);
-    if (nsteps <= 8 * NSM) {                           // one slice: the fused norm / SwiGLU need the whole row in one workgroup
-        *KS = 1;
-        *per = (nsteps + 7) / 8;
-        *gx_out = wgs < nblk ? wgs : nblk;
-        return;
-    }
-    const int ks_min = (nsteps + 8 * NSM - 1) / (8 * NSM);
-    int best_ks = ks_min, best_gx = 1;
-    double best_cost = 1e30;
-    for (int ks = ks_min; ks <= 4 * ks_min && ks <= wgs; ++ks) {
-        const int pw = (nsteps + 8 * ks - 1) / (8 * ks);
-        const int ns = mb_ns_for(pw, MB);
-        if (ns == 0 || nsteps < ns) continue;
-        int gx = wgs / ks;
-        if (gx < 1) gx = 1;
-        if (gx > nblk) gx = nblk;
-        const int blocks = (nblk + gx - 1) / gx;       // of the busiest workgroup
-        // time ~ the busiest workgroup's stream (blocks x fragments it LOADS, live or not) + a fixed cost per slice of slab traffic
-        const double cost = (double)blocks * ns * (1.0 + 0.02 * ks);
-        if (cost < best_cost) { best_cost = cost; best_ks = ks; best_gx = gx; }
-    }
-    *KS = best_ks;
-    *per = (nsteps + 8 * best_ks - 1) / (8 * best_ks);
-    *gx_out = best_gx;
-}
-
+// Geometry (slices, steps per wave, grid): mb_plan in host_plan.cpp.  BAGEL_MB_WGS overrides the workgroup count (tuning / tests).
 static int mb_wgs() {
-    static int wgs_env = -1, cus_of_dev[16] = {0};
+    static int wgs_env = -1;
     if (wgs_env < 0) {
         const char* e = getenv("BAGEL_MB_WGS");
         wgs_env = (e && atoi(e) > 0) ? atoi(e) : 0;
     }
     if (wgs_env) return wgs_env;
-    int dev = 0;
-    (void)hipGetDevice(&dev);
-    dev &= 15;
-    if (cus_of_dev[dev] == 0) {
-        int cus = 0;
-        (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
-        cus_of_dev[dev] = cus > 0 ? cus : 256;
-    }
-    return cus_of_dev[dev];
-}
-
-extern "C" int bagel_gemv_mb_workspace_bytes(int32_t N, int32_t K, int64_t* bytes) {
-    BAGEL_REQUIRE(bytes && N > 0 && K > 0 && (K % 32) == 0 && (N % 16) == 0, "gemv_mb_workspace_bytes: bad argument");
-    // the slice count depends on the device's CU count and on the row count (17..32 rows: slices of at most 8 x 14 steps, slabs of 32 rows): an upper
-    // bound that holds for every geometry the launcher may pick (4 x the minimum slice count of the 32-row form, 32-row slabs)
-    const int nsteps = K / 32;
-    const int ks_min = (nsteps + 8 * 14 - 1) / (8 * 14);
-    *bytes = nsteps <= 8 * 14 ? 0 : (int64_t)4 * ks_min * 32 * N * 4;
-    return BAGEL_OK;
+    int cus = 0;
+    return bagel_device_cus(&cus) == BAGEL_OK ? cus : 256;
 }
 
 template <int NS, bool NORM, int MB>
@@ -386,35 +322,25 @@ extern "C" int bagel_gemv_mb_bf16(const void* A, int64_t lda, const void* W, int
                                   void* C, int64_t ldc, const void* norm_w, float eps, int32_t M, int32_t N, int32_t K, int32_t epilogue,
                                   void* workspace, int64_t workspace_bytes, hipStream_t stream) {
     BAGEL_REQUIRE(A && W && C, "gemv_mb: null pointer");
-    BAGEL_REQUIRE(M >= 1 && M <= 32, "gemv_mb: M=%d not in [1,32]", M);
-    BAGEL_REQUIRE(K > 0 && (K % 32) == 0 && (lda % 8) == 0 && (ldw % 8) == 0, "gemv_mb: K %% 32 == 0 and 16-byte rows required");
-    BAGEL_REQUIRE(epilogue >= 0 && epilogue <= 3, "gemv_mb: unknown epilogue %d", epilogue);
-    BAGEL_REQUIRE(epilogue == EPI_SWIGLU16 ? ((N % 32) == 0 && !bias && !R) : (N % 16) == 0, "gemv_mb: N %% 16 (SwiGLU: N %% 32, no bias/residual)");
+    MbGeometry g;                                                   // shape checks, slices, steps per wave and grid: host_plan.cpp
+    if (int rc = mb_plan(M, N, K, epilogue, norm_w != nullptr, mb_wgs(), &g)) return rc;
+    BAGEL_REQUIRE((lda % 8) == 0 && (ldw % 8) == 0, "gemv_mb: K %% 32 == 0 and 16-byte rows required");
+    BAGEL_REQUIRE(epilogue != EPI_SWIGLU16 || (!bias && !R), "gemv_mb: N %% 16 (SwiGLU: N %% 32, no bias/residual)");
     BAGEL_REQUIRE((ldc % 4) == 0 && (ldr % 4) == 0, "gemv_mb: ldc/ldr must be multiples of 4");
     BAGEL_REQUIRE((((uintptr_t)A | (uintptr_t)W | (uintptr_t)norm_w) & 15) == 0 && (((uintptr_t)C | (uintptr_t)R | (uintptr_t)bias) & 7) == 0, "gemv_mb: alignment");
     MbParams p;
     p.A = (const bf16_t*)A; p.lda = lda; p.W = (const bf16_t*)W; p.ldw = ldw; p.bias = (const bf16_t*)bias;
     p.R = (const bf16_t*)R; p.ldr = ldr; p.C = (bf16_t*)C; p.ldc = ldc; p.norm_w = (const bf16_t*)norm_w; p.eps = eps;
     p.M = M; p.N = N; p.K = K; p.epi = epilogue;
-    const bool sw = epilogue == EPI_SWIGLU16;
-    const int MB = M > 16 ? 2 : 1;                                  // request blocks of 16 rows that share every weight fragment
+    const int MB = M > 16 ? 2 : 1, NS = g.NS;                       // request blocks of 16 rows that share every weight fragment; the instantiation that runs
     p.slab_rows = 16 * MB;
-    int gx = 1;
-    mb_geometry(N, K, mb_wgs(), MB, &p.per, &p.KS, &gx);
-    const int NS = mb_ns_for(p.per, MB);                            // the instantiation that runs; its fragments must fit the row
-    if (NS == 0 || K / 32 < NS) return bagel_set_error(BAGEL_ERR_UNSUPPORTED, "gemv_mb: K=%d (%d steps per wave) has no instantiation", K, p.per);
-    if (p.KS > 1) {
-        if (norm_w || sw) return bagel_set_error(BAGEL_ERR_UNSUPPORTED, "gemv_mb: fused RMSNorm / SwiGLU need the whole row in one slice (K=%d)", K);
+    p.per = g.per; p.KS = g.KS;
+    if (p.KS > 1)
         BAGEL_REQUIRE(workspace && ((uintptr_t)workspace & 15) == 0 && workspace_bytes >= (int64_t)p.KS * p.slab_rows * N * 4,
                       "gemv_mb: K=%d runs as %d slices and needs a 16-byte aligned fp32 workspace of %lld bytes (bagel_gemv_mb_workspace_bytes)", K, p.KS,
                       (long long)p.KS * p.slab_rows * N * 4);
-    }
     p.part = (float*)workspace;
-    if (sw) {                                                       // units are gate/up PAIRS of blocks
-        const int nunits = N / 32;
-        if (gx > nunits) gx = nunits;
-    }
-    const dim3 grid(gx, p.KS);
+    const dim3 grid(g.gx, p.KS);
     if (int rc = NS == 4 ? mb_launch<4>(p, MB, grid, stream) : NS == 10 ? mb_launch<10>(p, MB, grid, stream) : NS == 14 ? mb_launch<14>(p, MB, grid, stream)
                                                                                                              : mb_launch<19>(p, MB, grid, stream)) return rc;
     if (p.KS > 1) {

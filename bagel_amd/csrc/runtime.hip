@@ -45,6 +45,19 @@ int bagel_enable_lds(const void* func, int bytes, const char* what) {
     return BAGEL_OK;
 }
 
+int bagel_device_cus(int* cus) {
+    static int cus_of[64] = {0};           // a racing first call computes the same value twice
+    int dev = 0, n = 0;
+    if (hipGetDevice(&dev) != hipSuccess) return bagel_set_error(BAGEL_ERR_LAUNCH, "cannot query the current device");
+    const bool cached = dev >= 0 && dev < 64;
+    if (cached && cus_of[dev] > 0) n = cus_of[dev];
+    else if (hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n <= 0)
+        return bagel_set_error(BAGEL_ERR_LAUNCH, "cannot query the CU count of device %d", dev);
+    if (cached) cus_of[dev] = n;
+    *cus = n;
+    return BAGEL_OK;
+}
+
 extern "C" int bagel_hip_version(void) { return 100; }
 extern "C" const char* bagel_hip_last_error(void) { return g_err; }
 extern "C" const char* bagel_hip_arch(void) { return "gfx950"; }

@@ -178,46 +178,31 @@ MB_MAX_ROWS = min(MB_MAX_ROWS, int(os.environ.get("BAGEL_GEMV_MB_ROWS", MB_MAX_R
 _MB_WS = {}
 
 
-def _mb_slices(K, M=1):
-    """(steps per wave if the row runs as ONE K slice else None, minimum K slices) of bagel_gemv_mb_bf16 -- mirrors mb_geometry in
-    csrc/gemv_mb.hip (rows of more than 8 x 19 steps of 32 are cut over workgroups; the launcher picks the slice count between the
-    minimum and 4 x the minimum so that the column blocks divide evenly over the CUs).  M > 16 (two blocks of 16 request rows per wave): the
-    longest instantiation is 14 steps, so one slice holds 8 x 14 steps (K = 3584)."""
-    nsteps = K // 32
-    nsm = 14 if M > 16 else 19
-    if nsteps <= 8 * nsm:
-        return -(-nsteps // 8), 1
-    return None, -(-nsteps // (8 * nsm))
-
-
 def mb_workspace_floats(N, K):
     """fp32 elements of the K-slice workspace bagel_gemv_mb_bf16 may need for an [N, K] weight at ANY row count (bagel_gemv_mb_workspace_bytes: the bound
     of the 32-row form -- shorter slices, 32-row slabs); 0: the row runs in one slice whatever M is."""
-    per, ks = _mb_slices(K, 32)
-    return 0 if per is not None else 4 * ks * 32 * N
+    out = ctypes.c_int64(0)
+    check(lib().bagel_gemv_mb_workspace_bytes(N, K, ctypes.addressof(out)), "bagel_gemv_mb_workspace_bytes")
+    return out.value // 4
 
 
 def gemv_mb_supported(A, W, C, bias, residual, epilogue, has_norm, M=None):
     if not GEMV_MB:
         return False
     N, K = W.shape
-    if K % 32 or N % (32 if epilogue == EPI_SWIGLU16 else 16):
-        return False
     M = A.shape[0] if M is None else M
     if not 1 <= M <= MB_MAX_ROWS:
-        return False
-    per, ks = _mb_slices(K, M)
-    if per is not None:
-        ns = next(n for n in (4, 10, 14, 19) if per <= n)
-        if K // 32 < ns:
-            return False
-    elif has_norm or epilogue == EPI_SWIGLU16:
         return False
     if epilogue == EPI_SWIGLU16 and (bias is not None or residual is not None):
         return False
     ok = A.data_ptr() % 16 == 0 and W.data_ptr() % 16 == 0 and _ld(A) % 8 == 0 and W.stride(0) % 8 == 0 and C.data_ptr() % 8 == 0 and _ld(C) % 4 == 0
     ok = ok and (bias is None or bias.data_ptr() % 8 == 0)
-    return ok and (residual is None or (residual.data_ptr() % 8 == 0 and _ld(residual) % 4 == 0))
+    if not (ok and (residual is None or (residual.data_ptr() % 8 == 0 and _ld(residual) % 4 == 0))):
+        return False
+    # the shape verdict is the launcher's own (it does not depend on the workgroup count; 256 = an MI355X)
+    g = (ctypes.c_int32 * 3)()
+    return lib().bagel_gemv_mb_geometry(M, N, K, int(epilogue), int(bool(has_norm)), 256, ctypes.addressof(g), ctypes.addressof(g) + 4,
+                                        ctypes.addressof(g) + 8) == 0
 
 
 def gemv_mb(A, W, C, *, bias=None, residual=None, epilogue=EPI_NONE, M=None, norm_w=None, eps=0.0, workspace=None):
@@ -234,7 +219,7 @@ def gemv_mb(A, W, C, *, bias=None, residual=None, epilogue=EPI_NONE, M=None, nor
         _req(residual, BF16, "gemv_mb.residual")
     if norm_w is not None:
         _req(norm_w, BF16, "gemv_mb.norm_w")
-    need = mb_workspace_floats(N, K) * 4                # bagel_gemv_mb_workspace_bytes
+    need = mb_workspace_floats(N, K) * 4
     ws = workspace
     if need and ws is None:
         key = _ws_key(A.device)
@@ -297,45 +282,8 @@ def decode_engine_sync_words(n_phases):
     return n // 4
 
 
-def decode_engine_supported(phases):
-    """The shapes the persistent decode engine serves (csrc/engine.hip): what bagel_decode_engine_bf16 would refuse is refused here
-    without a launch, so callers can fall back to the launch form."""
-    if not 1 <= len(phases) <= 4:
-        return False
-    n_wg = lib().bagel_decode_engine_workgroups()
-    if n_wg <= 0:
-        return False
-    slot = max_k = 0
-    for ph in phases:
-        N, K = ph["W"].shape
-        if K % 8 or N % 2 or ph["W"].stride(0) % 8:
-            return False
-        if ph.get("norm_w") is not None and K > 4096:
-            return False
-        split = ph.get("norm_w") is None and K >= 8192 and N // 2 <= 8192
-        groups = -(-(K // 8) // 64)
-        unit_groups = -(-groups // 4) if split else groups
-        if 2 * unit_groups > 60:
-            return False
-        if split and -(-(N // 2) // n_wg) > 32:                                       # ENG_MAX_DPAIRS split-K pairs per workgroup
-            return False
-        if ph.get("epilogue", EPI_NONE) == EPI_SWIGLU16 and (N % 32 or ph.get("bias") is not None or ph.get("residual") is not None):
-            return False
-        for key, align in (("A", 16), ("W", 16), ("norm_w", 16), ("C", 4), ("residual", 4)):
-            t = ph.get(key)
-            if t is not None and t.data_ptr() % align:
-                return False
-        slot, max_k = max(slot, 2 * unit_groups * 1024), max(max_k, K)
-    # the LDS ring beside the activation vector and the sync block (ENG_LDS_MAX, ENG_SYNC_BYTES, ENG_MAX_SLOTS; two loaders own alternate slots)
-    nslot = min((160 * 1024 - (max_k * 2 + 1023) // 1024 * 1024 - 2560) // slot, 8)
-    nslot -= nslot % 2
-    return nslot >= 4
-
-
-def decode_engine(phases, eps, sync_ws, status, trace=None):
-    """ONE persistent launch for a chain of batch-1 projections; see bagel_decode_engine_bf16.  ``phases``: list of dicts with the keys of
-    ``gemv`` -- A, W, C and optionally bias, residual, norm_w, epilogue -- where A of phase i > 0 is C of phase i - 1.  ``sync_ws``: int32 /
-    uint32 words, at least decode_engine_sync_words(len(phases)), ZERO at launch; ``status``: 4 words, checked by the caller."""
+def _engine_args(phases):
+    """The ptrs / dims host arrays of bagel_decode_engine_bf16 / _check for a list of phase dicts."""
     n = len(phases)
     ptrs = (ctypes.c_void_p * (6 * n))()
     dims = (ctypes.c_int64 * (4 * n))()
@@ -355,6 +303,22 @@ def decode_engine(phases, eps, sync_ws, status, trace=None):
         ptrs[6 * i + 4] = _ptr(ph.get("residual"))
         ptrs[6 * i + 5] = _ptr(C)
         dims[4 * i + 0], dims[4 * i + 1], dims[4 * i + 2], dims[4 * i + 3] = N, K, W.stride(0), int(ph.get("epilogue", EPI_NONE))
+    return ptrs, dims
+
+
+def decode_engine_supported(phases):
+    """The shapes the persistent decode engine serves (csrc/engine.hip): what bagel_decode_engine_bf16 would refuse is refused here
+    without a launch (bagel_decode_engine_check), so callers can fall back to the launch form."""
+    ptrs, dims = _engine_args(phases)
+    return lib().bagel_decode_engine_check(ctypes.addressof(ptrs), ctypes.addressof(dims), len(phases)) == 0
+
+
+def decode_engine(phases, eps, sync_ws, status, trace=None):
+    """ONE persistent launch for a chain of batch-1 projections; see bagel_decode_engine_bf16.  ``phases``: list of dicts with the keys of
+    ``gemv`` -- A, W, C and optionally bias, residual, norm_w, epilogue -- where A of phase i > 0 is C of phase i - 1.  ``sync_ws``: int32 /
+    uint32 words, at least decode_engine_sync_words(len(phases)), ZERO at launch; ``status``: 4 words, checked by the caller."""
+    n = len(phases)
+    ptrs, dims = _engine_args(phases)
     if sync_ws.numel() * sync_ws.element_size() < 4 * decode_engine_sync_words(n) or sync_ws.element_size() != 4:
         raise BagelHipError("decode_engine: sync_ws is smaller than decode_engine_sync_words(len(phases)) 4-byte words")
     if status.numel() < 4 or status.element_size() != 4:

@@ -214,6 +214,12 @@ int bagel_gemm_skinny_bf16(const void* A, int64_t lda, const void* W, int64_t ld
  * (BAGEL_ERR_UNSUPPORTED).  Deterministic: fixed summation order, no atomics; a row's result does not depend on M within one block
  * count (M <= 16 / M > 16) -- across the two the K partition may differ (fp32 summation order), like the K-split tiles of bagel_gemm_bf16. */
 int bagel_gemv_mb_workspace_bytes(int32_t N, int32_t K, int64_t* bytes);
+/* The launcher's own shape verdict and launch geometry on `workgroups` persistent workgroups (the launcher uses the device's CU count), pure host
+ * code: 0 and per = 32-deep k-steps per wave, ks = K slices (> 1: workspace needed, no fused norm / SwiGLU16), gx = workgroups per slice; or the
+ * error bagel_gemv_mb_bf16 would report for this shape (BAGEL_ERR_UNSUPPORTED: no instantiation / a sliced row with norm or SwiGLU16).  The
+ * verdict does not depend on `workgroups`; per, ks and gx of a sliced row do. */
+int bagel_gemv_mb_geometry(int32_t M, int32_t N, int32_t K, int32_t epilogue, int32_t has_norm, int32_t workgroups, int32_t* per, int32_t* ks,
+                           int32_t* gx);
 int bagel_gemv_mb_bf16(const void* A, int64_t lda, const void* W, int64_t ldw, const void* bias, const void* R, int64_t ldr,
                        void* C, int64_t ldc, const void* norm_w, float eps, int32_t M, int32_t N, int32_t K, int32_t epilogue,
                        void* workspace, int64_t workspace_bytes, bagel_stream_t stream);
@@ -337,7 +343,7 @@ int bagel_attn_decode_fused_bf16(const void* qkv, int64_t ld, const void* cos_ta
                                  int32_t head_dim_padded, float eps, int32_t use_norm, float softmax_scale,
                                  bagel_stream_t stream);
 
-/* EXPERIMENTAL -- do NOT bind these four entry points in an integration: the persistent decode engine is a parity-tested
+/* EXPERIMENTAL -- do NOT bind these five entry points in an integration: the persistent decode engine is a parity-tested
  * NEGATIVE result (94.4 us per layer against 83.8 us for the four gemv launches it replaces, profiles/r05_decode_engine.log), off by default
  * (opt-in BAGEL_DECODE_ENGINE=1), kept for the record; the signatures may change or disappear.
  * A CHAIN of 1..4 dependent batch-1 projections as ONE persistent launch (csrc/engine.hip): phase i computes what
@@ -360,6 +366,9 @@ int bagel_decode_engine_workgroups(void);
 int bagel_decode_engine_sync_bytes(int32_t n_phases);
 int bagel_decode_engine_bf16(const void* const* ptrs, const int64_t* dims, int32_t n_phases, float eps, void* sync_ws, void* status,
                              bagel_stream_t stream);
+/* Everything bagel_decode_engine_bf16 does with ptrs / dims on the current device except the launch: 0 if it would launch this chain, else the
+ * same refusal (a caller then takes the launch form). */
+int bagel_decode_engine_check(const void* const* ptrs, const int64_t* dims, int32_t n_phases);
 /* Diagnostic form: the same launch, and every workgroup leaves its event times (100 MHz ticks of s_memrealtime) in
  * trace[workgroup][4 phases][16] uint64: 0 loader first issue, 1 last issue, 2 ticks blocked on a free ring slot, 3 ticks blocked in counted DMA
  * waits, 4 consumer 0 hand-off begin, 5 flags seen, 6 activation staged, 7..9 consumer c's last unit done, 10..12 ticks consumer c waited for

@@ -220,7 +220,7 @@ def test_vae_launch_wrappers_match_the_header(monkeypatch):
     ops.chw_bf16_to_u8(b(3, 4, 6))
     ops.gemv_mb(b(4, 128), b(64, 128), b(4, 64), M=4)
     assert calls == ["bagel_conv_gemm_bf16"] * 2 + ["bagel_groupnorm_bf16", "bagel_softmax_rows_bf16", "bagel_vae_reparam_bf16", "bagel_chw_bf16_to_u8",
-                     "bagel_gemv_mb_bf16"]
+                     "bagel_gemv_mb_workspace_bytes", "bagel_gemv_mb_bf16"]      # gemv_mb asks the library for its workspace bound, then launches
     # the FP8 option's delayed scales (with and without the saturated-row counter) and the fp8-output gate/up projection
     del calls[:]
     ops.fp8_delayed_scales(f(8), f(8), rows=torch.arange(4, dtype=torch.int32), margin=2.0, saturated=torch.zeros(1, dtype=torch.int32))
@@ -281,9 +281,9 @@ def test_ops_gemm_routing_of_the_vit_epilogues_and_small_row_counts(monkeypatch)
 
 
 def test_gemv_mb_workspace_mirror_matches_the_library():
-    """``ops.mb_workspace_floats`` / ``ops._mb_slices`` mirror csrc/gemv_mb.hip's geometry (the decode session sizes its K-slice workspace with the Python side,
-    the launcher checks it against its own arithmetic): the library's ``bagel_gemv_mb_workspace_bytes`` is a host-only function -- no GPU needed -- and must
-    agree for every row length the models use, incl. the round-6 bound of the two-block (17..32 rows) form: slices of at most 8 x 14 steps, 32-row slabs."""
+    """``ops.mb_workspace_floats`` / ``ops.gemv_mb_supported`` ask the library (csrc/host_plan.cpp: host-only functions -- no GPU needed) instead of restating
+    its geometry: the decode session sizes its K-slice workspace with ``bagel_gemv_mb_workspace_bytes`` for every row length the models use, incl. the round-6
+    bound of the two-block (17..32 rows) form -- slices of at most 8 x 14 steps, 32-row slabs -- and ``bagel_gemv_mb_geometry`` gives the launcher's own slices."""
     import ctypes
     from bagel_amd import _lib, ops
     L = _lib.lib()
@@ -291,10 +291,24 @@ def test_gemv_mb_workspace_mirror_matches_the_library():
         out = ctypes.c_int64(-1)
         assert L.bagel_gemv_mb_workspace_bytes(N, K, ctypes.byref(out)) == 0
         assert out.value == ops.mb_workspace_floats(N, K) * 4, (N, K, out.value)
-    # one slice up to 8 x 19 steps at <= 16 rows, up to 8 x 14 steps (K = 3584) at 17..32 rows; beyond that the minimum slice count
-    assert ops._mb_slices(3584, 16) == (14, 1) and ops._mb_slices(3584, 32) == (14, 1)
-    assert ops._mb_slices(4864, 16) == (19, 1) and ops._mb_slices(4864, 17) == (None, 2)
-    assert ops._mb_slices(18944, 16) == (None, 4) and ops._mb_slices(18944, 32) == (None, 6)
+        nsteps = K // 32
+        assert out.value == (0 if nsteps <= 112 else 4 * -(-nsteps // 112) * 32 * N * 4), (N, K, out.value)
+
+    def geometry(K, M, N=3584, wgs=256):
+        per, ks, gx = ctypes.c_int32(-1), ctypes.c_int32(-1), ctypes.c_int32(-1)
+        assert L.bagel_gemv_mb_geometry(M, N, K, 0, 0, wgs, ctypes.byref(per), ctypes.byref(ks), ctypes.byref(gx)) == 0, L.bagel_hip_last_error()
+        return per.value, ks.value, gx.value
+    # one slice up to 8 x 19 steps at <= 16 rows, up to 8 x 14 steps (K = 3584) at 17..32 rows; beyond that at least the minimum slice count
+    assert geometry(3584, 16)[:2] == (14, 1) and geometry(3584, 32)[:2] == (14, 1)
+    assert geometry(4864, 16)[:2] == (19, 1) and geometry(4864, 17)[1] >= 2
+    assert geometry(18944, 16)[1] >= 4 and geometry(18944, 32)[1] >= 6
+    # the 7B down projection as csrc/host_plan.cpp documents it: 8 slices x 32 workgroups, 10 steps per wave
+    for M in (2, 16):
+        assert geometry(18944, M, N=3584, wgs=256) == (10, 8, 32)
+    # a sliced row takes neither the fused norm nor SwiGLU16: the launcher's own refusal
+    out3 = (ctypes.c_int32 * 3)()
+    assert L.bagel_gemv_mb_geometry(16, 3584, 18944, 0, 1, 256, out3, ctypes.byref(out3, 4), ctypes.byref(out3, 8)) == -3
+    assert b"whole row in one slice" in L.bagel_hip_last_error()
     assert ops.MB_MAX_ROWS == 32
 
 

@@ -15,5 +15,7 @@ for f in $ROOT/bagel_amd/csrc/*.hip; do
   pids+=($!)
 done
 for p in "${pids[@]}"; do wait $p; done
+# the host-only planners: plain C++ (hipcc would take a .cpp for HIP), no device code
+( cd $ROOT/bagel_amd/csrc && hipcc ${FLAGS/--offload-arch=gfx950/} -x c++ -c host_plan.cpp -o $OUT/host_plan.o )
 hipcc -shared -fPIC --offload-arch=gfx950 -o $ROOT/bagel_amd/libbagel_hip_$TAG.so $OUT/*.o
 echo built $ROOT/bagel_amd/libbagel_hip_$TAG.so
