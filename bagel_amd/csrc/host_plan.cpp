@@ -206,6 +206,16 @@ int pq_leftover_split(int nblk, int wgs, int nk, size_t ws_bytes, int policy, in
     return best;
 }
 
+extern "C" int bagel_gemm_leftover_split(int32_t nblk, int32_t wgs, int32_t nk, int64_t ws_bytes, int32_t policy, int32_t force, int32_t* n_full,
+                                         int32_t* ksplit) {
+    BAGEL_REQUIRE(n_full && ksplit, "gemm_leftover_split: null pointer");
+    BAGEL_REQUIRE(nblk >= 0 && wgs >= 1 && nk >= 0 && ws_bytes >= 0, "gemm_leftover_split: bad argument");
+    int nf = 0;
+    *ksplit = pq_leftover_split(nblk, wgs, nk, (size_t)ws_bytes, policy, force, &nf);
+    *n_full = nf;
+    return BAGEL_OK;
+}
+
 // Geometry of gemv_mb.hip.  Instantiations: NS = 4 (short rows, K <= 1024: the tiny test models), 10, 14 (K = 3584 in one slice: 14 steps per wave at the 7B
 // hidden size), 19.  The launch is PERSISTENT: one workgroup per CU (its ~170 registers x 8 waves leave no room for a second one), each
 // taking an even share of the column blocks of its K slice, so the activation prologue is paid once per workgroup and launch.

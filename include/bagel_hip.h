@@ -60,6 +60,10 @@ int bagel_gemm_bf16_ws(const void* A, int64_t lda,
                        int64_t ldw, const void* R, int64_t ldr, void* C, int64_t ldc,
                        int32_t N, int32_t K, int32_t epilogue, int32_t variant, void* workspace, int64_t workspace_bytes,
                        bagel_stream_t stream);
+/* Host-only: the K-split rule of the persistent GEMM's last round (csrc/host_plan.cpp, pq_leftover_split) for `nblk` 256 x 256 tiles on `wgs`
+ * workgroups with `nk` 64-deep k-tiles and a workspace of `ws_bytes`; policy / force as BAGEL_GEMM_SPLIT_POLICY / _FORCE.  Writes the tiles that run
+ * un-split in full rounds and the number of K parts of every leftover tile (1: no split).  No device is touched. */
+int bagel_gemm_leftover_split(int32_t nblk, int32_t wgs, int32_t nk, int64_t ws_bytes, int32_t policy, int32_t force, int32_t* n_full, int32_t* ksplit);
 
 /* Qwen2RMSNorm (modeling_qwen2.py:54-59); expert_of_row (nullable) selects w1 for rows flagged 1
  * (input_layernorm_moe_gen etc., qwen2_navit.py:784-787,812-815,1079-1082). */

@@ -182,6 +182,8 @@ static long fuzz_pq() {
             CHECK(s >= 1, "pq: nblk %d wgs %d nk %d: split %d", nblk, wgs, nk, s);
             CHECK(s == 1 || (s <= nk / 4 && (size_t)rest * s * (256 * 1024) <= ws), "pq: nblk %d wgs %d nk %d ws %zu policy %d force %d: split %d", nblk, wgs,
                   nk, ws, policy, force, s);
+            int32_t nf2 = -1, s2 = -1;
+            CHECK(bagel_gemm_leftover_split(nblk, wgs, nk, (int64_t)ws, policy, force, &nf2, &s2) == 0 && nf2 == n_full && s2 == s, "pq: the entry point disagrees");
             ++n;
         }
     return n;
