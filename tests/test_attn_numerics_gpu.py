@@ -2,7 +2,7 @@
 per-element bound of tests/util_attn_ref.py (derived there from the number formats, validated on the CPU by tests/test_attn_ref_cpu.py).
 
 Forms: the tile kernel (``attn_varlen``), the planned persistent kernel with the five plans of tests/test_attn2_gpu.py (``attn_planned``: chip
-default, 8 workers, 16 workers with every partial round key-split, the split ring, the split ring with key splits), the ``ranges`` entry
+default, 8 workers, 16 workers with every partial round key-split, twice the chip's workers, the same with key splits), the ``ranges`` entry
 with ``lse`` (training), and paged decode attention (``attn_decode_paged``, also with two chunks per workgroup in a child process).
 Families: see ``util_attn_ref.build`` -- keyset (the key set of every row, checked exactly), pairing (key order of S against V^T), peaked,
 staircase (the deferred maximum and its rescale), split (combine weights, one of them underflowing), sink, pbias (lse).
@@ -23,7 +23,7 @@ from tests.test_ops_gpu import BF16, DEV, attention_device_inputs, ops
 pytestmark = pytest.mark.gpu
 
 PLANS = [("chip", dict()), ("w8", dict(n_workers=8)), ("w16_split", dict(n_workers=16, split_min_tiles=1)),
-         ("split_ring", dict(n_workers="2xchip")), ("split_ring_keysplit", dict(n_workers="2xchip", split_min_tiles=1))]
+         ("oversubscribed", dict(n_workers="2xchip")), ("oversubscribed_keysplit", dict(n_workers="2xchip", split_min_tiles=1))]
 PAD, GAP, SENTINEL = 3, 2, 7.0        # rows behind the last sample; rows in front of every sample in the ranges layout
 
 
@@ -123,7 +123,7 @@ def test_attention_forms_on_designed_inputs(si, hi, causal, family):
         a, b = bits(outs["varlen"])[keep], bits(outs[form])[keep]
         assert torch.equal(a, b), f"{what} [{form}]: un-split items must equal the tile kernel bit for bit ({int((a != b).any(-1).sum())} rows differ)"
     if si != 1:       # shapes with >= 5 key tiles: the key-split plans do split (the 34-row prompt has a single tile)
-        assert plans["w16_split"].n_comb > 0 and plans["split_ring_keysplit"].n_comb > 0
+        assert plans["w16_split"].n_comb > 0 and plans["oversubscribed_keysplit"].n_comb > 0
 
 
 # ------------------------------------------------------------------------------------------------------------

@@ -87,7 +87,7 @@ def case(name, q_lens, ctx_lens, nq, nkv, causal, iters, D=128, split_min_tiles=
     for nw, apx, outx, r in extra:
         tx = timeit(r, iters)
         dx = (outx.float() - out2.float()).abs().max().item()
-        print(f"{'':28s}   planned with {nw} workers ({'split 2+2 ring, 64 KB' if nw > CUS else 'unified ring'}) {tx:8.3f} ms {fl / tx / 1e9:7.1f} TF  ({t2 / tx:5.3f}x of the default)  "
+        print(f"{'':28s}   planned with {nw} workers{' (oversubscribed)' if nw > CUS else ''} {tx:8.3f} ms {fl / tx / 1e9:7.1f} TF  ({t2 / tx:5.3f}x of the default)  "
               f"max|d vs default| {dx:.3g}  items {apx.n_items} split {apx.n_comb} makespan {apx.makespan} ideal {apx.total / apx.n_workers:.1f}", flush=True)
 
 
@@ -100,15 +100,15 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--iters", type=int, default=20)
     ap.add_argument("--only", default=None)
-    ap.add_argument("--workers", type=int, nargs="*", default=[], help="extra plans with these worker counts (more than the CU count = the split-ring kernel, two workgroups per CU asked for)")
+    ap.add_argument("--workers", type=int, nargs="*", default=[], help="extra plans with these worker counts (more than the CU count = an oversubscribed plan: the surplus workgroups wait for a CU)")
     a = ap.parse_args()
     WORKERS[:] = a.workers
     CUS = torch.cuda.get_device_properties(0).multi_processor_count
     if a.workers:
         from bagel_amd import _lib
         L = _lib.lib()
-        print(f"CUs {CUS}; resident workgroups per CU by the runtime's occupancy calculator: head_dim 128 unified ring {L.bagel_debug_attn_occupancy(128, 0)}, "
-              f"split ring {L.bagel_debug_attn_occupancy(128, 1)}; head_dim 64 unified {L.bagel_debug_attn_occupancy(64, 0)}, split {L.bagel_debug_attn_occupancy(64, 1)}", flush=True)
+        print(f"CUs {CUS}; resident workgroups per CU by the runtime's occupancy calculator: head_dim 128: {L.bagel_debug_attn_occupancy(128)}, "
+              f"head_dim 64: {L.bagel_debug_attn_occupancy(64)}", flush=True)
     cases = [("denoise_b8 (configs[2])", [4098] * 8, [32] * 4 + [0] * 4, 28, 4, False),
              ("denoise_b4 (one stream)", [4098] * 4, [32] * 4, 28, 4, False),
              ("edit_3streams (configs[4])", [4098] * 3, [9032, 9000, 32], 28, 4, False),
