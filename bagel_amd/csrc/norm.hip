@@ -87,7 +87,7 @@ __global__ __launch_bounds__(256) void rmsnorm_kernel(const bf16_t* __restrict__
 
 extern "C" int bagel_rmsnorm_bf16(const void* x, int64_t ldx, const void* w0, const void* w1, const int32_t* expert_of_row,
                                   void* y, int64_t ldy, int32_t rows, int32_t cols, float eps, hipStream_t stream) {
-    BAGEL_REQUIRE(x && y && w0, "rmsnorm: null pointer");
+    BAGEL_REQUIRE(rows <= 0 || (x && y && w0), "rmsnorm: null pointer");   // an empty tensor has no storage
     BAGEL_REQUIRE(cols > 0 && cols % 8 == 0 && ldx % 8 == 0 && ldy % 8 == 0, "rmsnorm: cols/ld must be multiples of 8");
     BAGEL_REQUIRE(!expert_of_row || w1, "rmsnorm: expert routing needs w1");
     if (rows <= 0) return BAGEL_OK;
@@ -187,7 +187,7 @@ __global__ __launch_bounds__(256) void rmsnorm_fp8_kernel(const bf16_t* __restri
 
 extern "C" int bagel_rmsnorm_fp8(const void* x, int64_t ldx, const void* w, void* q, int64_t ldq_bytes, float* scale, int32_t rows,
                                  int32_t cols, float eps, hipStream_t stream) {
-    BAGEL_REQUIRE(x && q && w && scale, "rmsnorm_fp8: null pointer");
+    BAGEL_REQUIRE(rows <= 0 || (x && q && w && scale), "rmsnorm_fp8: null pointer");
     BAGEL_REQUIRE(cols > 0 && cols % 8 == 0 && ldx % 8 == 0 && ldq_bytes % 8 == 0, "rmsnorm_fp8: cols/ld must be multiples of 8");
     if (rows <= 0) return BAGEL_OK;
     hipLaunchKernelGGL(rmsnorm_fp8_kernel, dim3(ceil_div(rows, 4)), dim3(256), 0, stream, (const bf16_t*)x, (long)ldx, (const bf16_t*)w,
@@ -237,7 +237,7 @@ __global__ __launch_bounds__(256) void layernorm_kernel(const bf16_t* __restrict
 
 extern "C" int bagel_layernorm_bf16(const void* x, int64_t ldx, const void* w, const void* b, void* y, int64_t ldy,
                                     int32_t rows, int32_t cols, float eps, hipStream_t stream) {
-    BAGEL_REQUIRE(x && y && w && b, "layernorm: null pointer");
+    BAGEL_REQUIRE(rows <= 0 || (x && y && w && b), "layernorm: null pointer");
     BAGEL_REQUIRE(cols > 0 && cols % 8 == 0 && ldx % 8 == 0 && ldy % 8 == 0, "layernorm: cols/ld must be multiples of 8");
     if (rows <= 0) return BAGEL_OK;
     hipLaunchKernelGGL(layernorm_kernel, dim3(ceil_div(rows, 4)), dim3(256), 0, stream, (const bf16_t*)x, (long)ldx,
@@ -258,7 +258,7 @@ __global__ void rope_table_kernel(const long* __restrict__ pos, const float* __r
 
 extern "C" int bagel_rope_table(const int64_t* position_ids, const float* inv_freq, void* cos_out, void* sin_out,
                                 int32_t rows, int32_t half_dim, hipStream_t stream) {
-    BAGEL_REQUIRE(position_ids && inv_freq && cos_out && sin_out, "rope_table: null pointer");
+    BAGEL_REQUIRE(rows <= 0 || (position_ids && inv_freq && cos_out && sin_out), "rope_table: null pointer");
     if (rows <= 0) return BAGEL_OK;
     const int n = rows * half_dim;
     hipLaunchKernelGGL(rope_table_kernel, dim3(ceil_div(n, 256)), dim3(256), 0, stream, (const long*)position_ids, inv_freq,
@@ -372,7 +372,7 @@ extern "C" int bagel_qknorm_rope_bf16(void* qkv, int64_t ld, const void* cos_tab
                                       const void* k_w0, const void* q_w1, const void* k_w1, const int32_t* expert_of_row,
                                       int32_t rows, int32_t nq, int32_t nkv, int32_t head_dim, int32_t head_dim_padded,
                                       float eps, int32_t gen_mode, int32_t use_norm, hipStream_t stream) {
-    BAGEL_REQUIRE(qkv && cos_tab && sin_tab, "qknorm_rope: null pointer");
+    BAGEL_REQUIRE(rows <= 0 || (qkv && cos_tab && sin_tab), "qknorm_rope: null pointer");
     BAGEL_REQUIRE(!use_norm || (q_w0 && k_w0), "qknorm_rope: norm weights missing");
     BAGEL_REQUIRE(!expert_of_row || !use_norm || (q_w1 && k_w1), "qknorm_rope: expert routing needs the second weight set");
     BAGEL_REQUIRE(head_dim_padded >= head_dim && ld % 2 == 0, "qknorm_rope: bad head_dim_padded/ld");
@@ -421,7 +421,7 @@ __global__ __launch_bounds__(256) void rope2d_kernel(bf16_t* __restrict__ qkv, l
 extern "C" int bagel_rope2d_bf16(void* qkv, int64_t ld, const void* cos_h, const void* sin_h, const void* cos_w, const void* sin_w,
                                  const int64_t* pos_ids, int64_t rows, int32_t nheads, int32_t head_dim, int32_t head_dim_padded,
                                  hipStream_t stream) {
-    BAGEL_REQUIRE(qkv && cos_h && sin_h && cos_w && sin_w && pos_ids, "rope2d: null pointer");
+    BAGEL_REQUIRE(rows <= 0 || (qkv && cos_h && sin_h && cos_w && sin_w && pos_ids), "rope2d: null pointer");
     BAGEL_REQUIRE(head_dim > 0 && head_dim % 4 == 0 && head_dim <= head_dim_padded, "rope2d: head_dim %d must be a multiple of 4", head_dim);
     if (rows <= 0 || nheads <= 0) return BAGEL_OK;
     const long total = rows * nheads * (head_dim / 2);
