@@ -298,6 +298,68 @@ extern "C" int bagel_gemv_mb_workspace_bytes(int32_t N, int32_t K, int64_t* byte
     return BAGEL_OK;
 }
 
+// Geometry of gemv_mb_w4.hip.  A row of K / 128 k-steps is G = ceil(steps / 4) scale groups; a wave holds the activation fragments of gpw = 1 or 2 groups
+// (instantiations NS = 4, 8 k-steps: 8 VGPRs per step and request block), so one workgroup covers up to 16 groups (K <= 8192: every K = 3584 projection of the 7B
+// model runs as 7 live waves x 1 group).  Longer rows are cut into KS slices of gps = ceil(G / KS) groups; as for gemv_mb, KS is chosen together with the
+// workgroups per slice by the busiest workgroup's stream: the 7B down projection (148 steps = 37 groups, 224 blocks, 256 CUs) runs as 5 slices (8, 8, 8, 8, 5
+// groups) x 51 workgroups x 4-5 blocks x 4 steps per wave.
+static const int MBW4_MAX_GPW = 2;
+
+static int mbw4_ks_min(int G) { return (G + 8 * MBW4_MAX_GPW - 1) / (8 * MBW4_MAX_GPW); }
+
+int mbw4_plan(int M, int N, int K, int epilogue, int wgs, MbW4Geometry* g) {
+    BAGEL_REQUIRE(g, "gemv_mb_w4: null geometry");
+    BAGEL_REQUIRE(M >= 1 && M <= 32, "gemv_mb_w4: M=%d not in [1,32]", M);
+    BAGEL_REQUIRE(K > 0 && (K % 128) == 0, "gemv_mb_w4: K=%d must be a multiple of 128", K);
+    BAGEL_REQUIRE(epilogue == BAGEL_EPI_NONE || epilogue == BAGEL_EPI_SWIGLU16, "gemv_mb_w4: epilogue %d not in {none, swiglu16}", epilogue);
+    const bool sw = epilogue == BAGEL_EPI_SWIGLU16;
+    BAGEL_REQUIRE(N > 0 && N % (sw ? 32 : 16) == 0, "gemv_mb_w4: N=%d must be a multiple of 16 (SwiGLU: 32)", N);
+    BAGEL_REQUIRE(wgs >= 1, "gemv_mb_w4: %d workgroups", wgs);
+    const int nsteps = K / 128, G = (nsteps + 3) / 4;
+    const int nunits = N / (sw ? 32 : 16);                          // what the workgroups of a slice share out: blocks (SwiGLU: gate/up pairs of blocks)
+    MbW4Geometry o;
+    o.MB = M > 16 ? 2 : 1;
+    if (G <= 8 * MBW4_MAX_GPW) {
+        o.KS = 1; o.gps = G; o.gpw = (G + 7) / 8;
+        o.gx = wgs < nunits ? wgs : nunits;
+    } else {
+        const int ks_min = mbw4_ks_min(G);
+        double best = 1e30;
+        o.KS = ks_min; o.gps = (G + ks_min - 1) / ks_min; o.gx = 1;
+        for (int ks = ks_min; ks <= 4 * ks_min; ++ks) {
+            const int gps = (G + ks - 1) / ks;
+            if ((long)(ks - 1) * gps >= G) continue;                // no empty slice
+            const int gpw = (gps + 7) / 8;
+            int gx = wgs / ks;
+            gx = gx < 1 ? 1 : (gx > nunits ? nunits : gx);
+            const int units = (nunits + gx - 1) / gx;               // of the busiest workgroup
+            const double cost = (double)units * gpw * (1.0 + 0.02 * ks);
+            if (cost < best) { best = cost; o.KS = ks; o.gps = gps; o.gx = gx; }
+        }
+        o.gpw = (o.gps + 7) / 8;
+    }
+    o.NS = 4 * o.gpw;
+    *g = o;
+    return BAGEL_OK;
+}
+
+extern "C" int bagel_gemv_mb_w4_geometry(int32_t M, int32_t N, int32_t K, int32_t epilogue, int32_t workgroups, int32_t* per, int32_t* slice_steps,
+                                         int32_t* ks, int32_t* gx) {
+    BAGEL_REQUIRE(per && slice_steps && ks && gx, "gemv_mb_w4_geometry: null pointer");
+    MbW4Geometry g;
+    if (int rc = mbw4_plan(M, N, K, epilogue, workgroups, &g)) return rc;
+    *per = g.NS; *slice_steps = 4 * g.gps; *ks = g.KS; *gx = g.gx;
+    return BAGEL_OK;
+}
+
+extern "C" int bagel_gemv_mb_w4_workspace_bytes(int32_t N, int32_t K, int64_t* bytes) {
+    BAGEL_REQUIRE(bytes && N > 0 && K > 0 && (K % 128) == 0 && (N % 16) == 0, "gemv_mb_w4_workspace_bytes: bad argument");
+    // an upper bound for every M and workgroup count: the planner tries at most 4 x the minimum slice count, slabs have at most 32 rows
+    const int G = (K / 128 + 3) / 4;
+    *bytes = G <= 8 * MBW4_MAX_GPW ? 0 : (int64_t)4 * mbw4_ks_min(G) * 32 * N * 4;
+    return BAGEL_OK;
+}
+
 // Per-phase validation and LDS-ring geometry of the decode engine (engine.hip).
 int eng_geometry(const void* const* ptrs, const int64_t* dims, int n_phases, int n_wg, int want_slots, int waves, int loaders, int depth,
                  EngGeometry* out) {

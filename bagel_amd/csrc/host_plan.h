@@ -55,6 +55,27 @@ void mb_geometry(int N, int K, int wgs, int MB, int* per, int* KS, int* gx_out);
 // the shape verdict of bagel_gemv_mb_bf16 on `wgs` workgroups: 0 and the geometry, or the refusal the launcher reports
 int mb_plan(int M, int N, int K, int epilogue, bool has_norm, int wgs, MbGeometry* g);
 
+// ---- gemv_mb_w4.hip: the same stream on MXFP4 codes.  K is counted in 128-deep k-steps and handed out in scale groups of four (one scale dword per lane):
+//      a slice (gridDim.y) takes gps groups, each of its 8 waves gpw of them (NS = 4 gpw fragments per wave: the instantiation) ----
+#ifdef __HIPCC__
+#define BAGEL_HD __host__ __device__
+#else
+#define BAGEL_HD
+#endif
+struct MbW4Geometry { int NS, gpw, gps, KS, gx, MB; };
+// k-steps [*s0, *s0 + *ns) of wave `wave` of slice `slice` (*ns == 0: the wave has no work; *s0 is a multiple of 4 either way): the kernel and the fuzz program share it
+BAGEL_HD static inline void mbw4_wave_steps(int gpw, int gps, int nsteps, int slice, int wave, int* s0, int* ns) {
+    const int G = (nsteps + 3) >> 2;
+    int g0 = slice * gps + wave * gpw, g1 = g0 + gpw;
+    const int gend = (slice + 1) * gps < G ? (slice + 1) * gps : G;
+    g1 = g1 < gend ? g1 : gend;
+    *s0 = 4 * g0;
+    const int s1 = 4 * g1 < nsteps ? 4 * g1 : nsteps;
+    *ns = g0 < g1 ? s1 - 4 * g0 : 0;
+}
+// the shape verdict of bagel_gemv_mb_w4_bf16 on `wgs` workgroups: 0 and the geometry, or the refusal the launcher reports (g is then untouched)
+int mbw4_plan(int M, int N, int K, int epilogue, int wgs, MbW4Geometry* g);
+
 // ---- engine.hip: per-phase unit form and the LDS ring beside the activation vector and the sync block ----
 #define ENG_MAXPH 4
 #define ENG_MAX_SLOTS 8

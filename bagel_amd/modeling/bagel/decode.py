@@ -163,8 +163,14 @@ class DecodeSession:
         if weight_quant == "mxfp4":
             if eng.H % 128 or eng.I % 128 or (nq * dp) % 128:
                 raise NotImplementedError("mxfp4 weights need row lengths that are multiples of 128")
-            if B > 4:
-                raise NotImplementedError("mxfp4 weights: the projection kernel quantises at most 4 activation rows per launch (batch <= 4)")
+            if B > ops.W4_GEMV_MAX_ROWS:
+                # more than four requests: the activation rows are quantised by a launch of their own (e4m3 + one scale per row) into buffers the session owns
+                # (stable pointers for the hipGraph); 5..32 requests then stream the codes (csrc/gemv_mb_w4.hip), more take ops.gemm_w4
+                self.aq8 = torch.empty((B, max(eng.H, eng.I, nq * dp)), dtype=torch.uint8, device=dev)
+                self.sa = torch.empty((B,), dtype=torch.float32, device=dev)
+                shapes = [((nq + 2 * nkv) * dp, eng.H), (eng.H, nq * dp), (2 * eng.I, eng.H), (eng.H, eng.I)]
+                self.mb_w4_ws = (torch.empty(max(max(ops.mb_w4_workspace_floats(n, k) for n, k in shapes), 4), dtype=torch.float32, device=dev)
+                                 if B <= ops.MB_W4_MAX_ROWS else None)
         self.w8 = self._quantised_weights() if weight_quant else None
         # OPT-IN (BAGEL_DECODE_ENGINE=1; the default is the launch form, which measured faster: csrc/engine.hip, profiles/r05_decode_engine.log).  One
         # request on bf16 weights: o_proj -> norm + gate/up -> down -> the next layer's norm + qkv (the last layer: final norm + lm_head) run as ONE
@@ -253,7 +259,19 @@ class DecodeSession:
         def proj(inp, w, out, norm_w=None, **kw):
             if isinstance(w, tuple):        # int8: (u8 weights, fp32 row scales); mxfp4: (E2M1 codes, E8M0 block scales)
                 if self.weight_quant == "mxfp4":
-                    return ops.gemv_w4(inp, w[0], w[1], out, norm_w=norm_w, eps=eng.eps, M=B, **kw)
+                    if B <= ops.W4_GEMV_MAX_ROWS:
+                        return ops.gemv_w4(inp, w[0], w[1], out, norm_w=norm_w, eps=eng.eps, M=B, **kw)
+                    # qkv / gate+up: rmsnorm_fp8 + product; o / down: quantize_rows_fp8 + product -- two launches per projection
+                    aq, sa = self.aq8[:, :inp.shape[-1]], self.sa
+                    if norm_w is not None:
+                        ops.rmsnorm_fp8(inp, norm_w, aq, sa, eng.eps)
+                    else:
+                        ops.quantize_rows_fp8(inp, aq, sa)
+                    bias, res, epi = kw.get("bias"), kw.get("residual"), kw.get("epilogue", ops.EPI_NONE)
+                    if B <= ops.MB_W4_MAX_ROWS and ops.gemv_mb_w4_supported(aq, w[0], w[1], out, bias, res, epi, M=B):
+                        return ops.gemv_mb_w4(aq, sa, w[0], w[1], out, bias=bias, residual=res, epilogue=epi, M=B, workspace=self.mb_w4_ws)
+                    # more than 32 requests, a refused shape or BAGEL_GEMV_MB_W4=0: the large-M kernel (few tiles at these row counts: the correctness fallback)
+                    return ops.gemm_w4(aq, sa, w[0], w[1], out, bias=bias, residual=res, epilogue=epi, M=B)
                 if self.weight_quant == "nf4":
                     return ops.gemv_nf4(inp, w[0], w[1], out, norm_w=norm_w, eps=eng.eps, M=B, **kw)
                 return ops.gemv_w8(inp, w[0], w[1], out, norm_w=norm_w, eps=eng.eps, M=B, **kw)

@@ -547,6 +547,78 @@ def gemm_w4(Aq, sa, Wq, Ws, C, *, bias=None, rows=None, M=None, residual=None, e
     return C
 
 
+W4_GEMV_MAX_ROWS = 4       # bagel_gemv_w4_bf16 quantises at most four activation rows in its prologue
+MB_W4_MAX_ROWS = 32
+_MB_W4_WS = {}
+
+
+def gemv_mb_w4_enabled():
+    """BAGEL_GEMV_MB_W4=0: 5..32 rows on MXFP4 weights go to ``gemm_w4`` instead of the weight stream (same-box A/B of the batched decode step); read per call."""
+    return os.environ.get("BAGEL_GEMV_MB_W4", "1") != "0"
+
+
+def mb_w4_workspace_floats(N, K):
+    """fp32 elements of the K-slice workspace bagel_gemv_mb_w4_bf16 may need for [N, K] MXFP4 weights at ANY row count (bagel_gemv_mb_w4_workspace_bytes);
+    0: the row runs in one slice whatever M is."""
+    out = ctypes.c_int64(0)
+    check(lib().bagel_gemv_mb_w4_workspace_bytes(N, K, ctypes.addressof(out)), "bagel_gemv_mb_w4_workspace_bytes")
+    return out.value // 4
+
+
+def gemv_mb_w4_supported(Aq, Wq, Ws, C, bias, residual, epilogue, M=None):
+    if not gemv_mb_w4_enabled():
+        return False
+    N, K = Wq.shape[0], Wq.shape[1] * 2
+    M = Aq.shape[0] if M is None else M
+    if not 1 <= M <= MB_W4_MAX_ROWS:
+        return False
+    if epilogue == EPI_SWIGLU16 and (bias is not None or residual is not None):
+        return False
+    ok = Aq.data_ptr() % 16 == 0 and Wq.data_ptr() % 16 == 0 and Ws.data_ptr() % 4 == 0 and Aq.stride(0) % 16 == 0 and Wq.stride(0) % 16 == 0
+    ok = ok and Ws.stride(0) % 4 == 0 and Ws.stride(0) >= ((K // 128 + 3) // 4) * 16 and C.data_ptr() % 8 == 0 and _ld(C) % 4 == 0
+    ok = ok and (bias is None or bias.data_ptr() % 8 == 0)
+    if not (ok and (residual is None or (residual.data_ptr() % 8 == 0 and _ld(residual) % 4 == 0))):
+        return False
+    # the shape verdict is the launcher's own (it does not depend on the workgroup count; 256 = an MI355X)
+    g = (ctypes.c_int32 * 4)()
+    a = ctypes.addressof(g)
+    return lib().bagel_gemv_mb_w4_geometry(M, N, K, int(epilogue), 256, a, a + 4, a + 8, a + 12) == 0
+
+
+def gemv_mb_w4(Aq, sa, Wq, Ws, C, *, bias=None, residual=None, epilogue=EPI_NONE, M=None, workspace=None):
+    """C[M <= 32, N] = epilogue(sa * (Aq @ dequant(Wq, Ws)^T)): ``gemm_w4``'s product (e4m3 activations with row scales x MXFP4 weights on the block-scaled
+    MFMA) as the batched-decode weight stream (bagel_gemv_mb_w4_bf16): the waves of a workgroup partition K and hold their activation fragments in registers
+    (one or two blocks of 16 rows).  Long rows (K > 8192: the 7B down projection) run as K slices through an fp32 workspace (``workspace`` or a
+    per-(device, stream) one) and a second, tiny launch."""
+    _req(Aq, torch.uint8, "gemv_mb_w4.Aq"); _req(Wq, torch.uint8, "gemv_mb_w4.Wq"); _req(Ws, torch.uint8, "gemv_mb_w4.Ws"); _req(C, BF16, "gemv_mb_w4.C")
+    _req(sa, torch.float32, "gemv_mb_w4.sa")
+    N, K = Wq.shape[0], Wq.shape[1] * 2
+    if Aq.shape[-1] != K or Ws.shape[0] != N or sa.numel() < Aq.shape[0]:
+        raise BagelHipError("gemv_mb_w4: shape mismatch")
+    if M is None:
+        M = Aq.shape[0]
+    if M > Aq.shape[0] or M > C.shape[0] or (residual is not None and M > residual.shape[0]):
+        raise BagelHipError(f"gemv_mb_w4: M={M} exceeds the rows of Aq / C / residual")
+    if residual is not None:
+        _req(residual, BF16, "gemv_mb_w4.residual")
+    if bias is not None:
+        _req(bias, BF16, "gemv_mb_w4.bias")
+    # (a shape the launcher refuses gets ITS message, not the workspace query's)
+    need = mb_w4_workspace_floats(N, K) * 4 if K > 0 and N > 0 and K % 128 == 0 and N % 16 == 0 else 0
+    ws = workspace
+    if need and ws is None:
+        key = _ws_key(Aq.device)
+        ws = _MB_W4_WS.get(key)
+        if ws is None or ws.numel() * 4 < need:
+            ws = _MB_W4_WS[key] = torch.empty(max(need // 4, 1 << 20), dtype=torch.float32, device=Aq.device)
+    if ws is not None:
+        _req(ws, torch.float32, "gemv_mb_w4.workspace")
+    check(lib().bagel_gemv_mb_w4_bf16(_ptr(Aq), Aq.stride(0), _ptr(sa), _ptr(Wq), Wq.stride(0), _ptr(Ws), Ws.stride(0), _ptr(bias), _ptr(residual),
+                                      _ld(residual) if residual is not None else 0, _ptr(C), _ld(C), M, N, K, epilogue,
+                                      _ptr(ws) if need else None, ws.numel() * 4 if need else 0, _stream()), "bagel_gemv_mb_w4_bf16")
+    return C
+
+
 KV_PAGE = 64          # tokens per KV page (BAGEL_KV_PAGE in decode.hip)
 DECODE_CHUNK = 64     # smallest keys-per-split the library may use (DEC_CH 128, or 64 with BAGEL_DEC_CH=64): sizes the workspace
 

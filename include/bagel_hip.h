@@ -280,6 +280,24 @@ int bagel_gemv_w4_bf16(const void* A, int64_t lda, const void* Wq, int64_t ldq_b
 int bagel_gemm_w4_bf16(const void* Aq, int64_t lda_bytes, const float* sa, const void* Wq, int64_t ldq_bytes, const void* Ws,
                        int64_t lds_bytes, const void* bias, const int32_t* a_rows, const int32_t* c_rows, int32_t M, const void* R,
                        int64_t ldr, void* C, int64_t ldc, int32_t N, int32_t K, int32_t epilogue, bagel_stream_t stream);
+/* The same product for 1..32 rows as a pure weight stream (batched decode on MXFP4 weights: 5..32 concurrent requests, which bagel_gemv_w4_bf16
+ * refuses): C[m, :] = epilogue(sa[m] * sum_k Aq[m, k] * (E2M1(code[n, k]) * 2^(sb[n, k/32] - 127))), operands exactly as bagel_gemm_w4_bf16 takes
+ * them (no row lists).  bagel_gemv_mb_bf16's form: the 8 waves of a persistent workgroup partition K in scale groups of four 128-deep steps and
+ * keep their e4m3 activation fragments in registers (one block of 16 rows, or two), every code byte is loaded once, straight into the FP4 operand
+ * layout of v_mfma_scale_f32_16x16x128_f8f6f4.  Epilogues none (+bias, +residual; R == C allowed) / SwiGLU16 (3) with the rounding points of
+ * bagel_gemm_w4_bf16.  K % 128 == 0, N % 16 == 0 (SwiGLU16: N % 32 == 0, no bias / residual); lda / ldq / lds in bytes.  Rows longer than 8192
+ * elements run as K slices over workgroups through a caller-owned fp32 workspace (bagel_gemv_mb_w4_workspace_bytes: an upper bound for every M;
+ * 16-byte aligned; only touched by this call) and a second small launch.  Deterministic: fixed summation order, no atomics; a row's result does
+ * not depend on the other rows or on M. */
+int bagel_gemv_mb_w4_workspace_bytes(int32_t N, int32_t K, int64_t* bytes);
+/* The launcher's own shape verdict and launch geometry on `workgroups` persistent workgroups, pure host code: 0 and per = 128-deep k-steps per
+ * wave (4 or 8: the instantiation), slice_steps = k-steps per K slice (whole scale groups), ks = K slices (> 1: workspace needed), gx =
+ * workgroups per slice; or the argument error bagel_gemv_mb_w4_bf16 would report for this shape. */
+int bagel_gemv_mb_w4_geometry(int32_t M, int32_t N, int32_t K, int32_t epilogue, int32_t workgroups, int32_t* per, int32_t* slice_steps,
+                              int32_t* ks, int32_t* gx);
+int bagel_gemv_mb_w4_bf16(const void* Aq, int64_t lda_bytes, const float* sa, const void* Wq, int64_t ldq_bytes, const void* Ws,
+                          int64_t lds_bytes, const void* bias, const void* R, int64_t ldr, void* C, int64_t ldc, int32_t M, int32_t N,
+                          int32_t K, int32_t epilogue, void* workspace, int64_t workspace_bytes, bagel_stream_t stream);
 
 /* FP8 (OCP e4m3) path for the gen-expert GEMMs of the denoise forward (the MI355X-native counterpart of the reference's quantised
  * load modes, app.py:114-131 -- an OPTION that changes results; bf16 is the default).
