@@ -360,6 +360,68 @@ extern "C" int bagel_gemv_mb_w4_workspace_bytes(int32_t N, int32_t K, int64_t* b
     return BAGEL_OK;
 }
 
+// Geometry of gemv_mb_nf4.hip.  A row is G = K / 128 k-groups (64 code bytes and two absmax blocks per weight row); a wave holds the activation fragments of
+// gpw <= 4 groups (instantiations GP = 1, 2, 4: 16 VGPRs per group and request block), so one workgroup covers up to 32 groups (K <= 4096: every K = 3584
+// projection of the 7B model runs as 7 live waves x 4 groups).  Longer rows are cut into KS slices of gps = ceil(G / KS) groups; as for gemv_mb, KS is chosen
+// together with the workgroups per slice by the busiest workgroup's stream (units x the fragments a wave of it holds): the 7B down projection (148 groups,
+// 224 blocks, 256 CUs) runs as 10 slices (15 groups, the last 13) x 25 workgroups x 8-9 blocks x 2 groups per wave.
+static const int MBNF4_MAX_GPW = 4;
+
+static int mbnf4_ks_min(int G) { return (G + 8 * MBNF4_MAX_GPW - 1) / (8 * MBNF4_MAX_GPW); }
+static int mbnf4_gp_for(int gpw) { return gpw <= 1 ? 1 : (gpw <= 2 ? 2 : 4); }
+
+int mbnf4_plan(int M, int N, int K, int epilogue, int wgs, MbNf4Geometry* g) {
+    BAGEL_REQUIRE(g, "gemv_mb_nf4: null geometry");
+    BAGEL_REQUIRE(M >= 1 && M <= 32, "gemv_mb_nf4: M=%d not in [1,32]", M);
+    BAGEL_REQUIRE(K > 0 && (K % 128) == 0, "gemv_mb_nf4: K=%d must be a multiple of 128", K);
+    BAGEL_REQUIRE(epilogue == BAGEL_EPI_NONE || epilogue == BAGEL_EPI_SWIGLU16, "gemv_mb_nf4: epilogue %d not in {none, swiglu16}", epilogue);
+    const bool sw = epilogue == BAGEL_EPI_SWIGLU16;
+    BAGEL_REQUIRE(N > 0 && N % (sw ? 32 : 16) == 0, "gemv_mb_nf4: N=%d must be a multiple of 16 (SwiGLU: 32)", N);
+    BAGEL_REQUIRE(wgs >= 1, "gemv_mb_nf4: %d workgroups", wgs);
+    const int G = K / 128;
+    const int nunits = N / (sw ? 32 : 16);                          // what the workgroups of a slice share out: blocks (SwiGLU: gate/up pairs of blocks)
+    MbNf4Geometry o;
+    o.MB = M > 16 ? 2 : 1;
+    if (G <= 8 * MBNF4_MAX_GPW) {
+        o.KS = 1; o.gps = G;
+        o.gx = wgs < nunits ? wgs : nunits;
+    } else {
+        const int ks_min = mbnf4_ks_min(G);
+        double best = 1e30;
+        o.KS = ks_min; o.gps = (G + ks_min - 1) / ks_min; o.gx = 1;
+        for (int ks = ks_min; ks <= 4 * ks_min; ++ks) {
+            const int gps = (G + ks - 1) / ks;
+            if ((long)(ks - 1) * gps >= G) continue;                // no empty slice
+            int gx = wgs / ks;
+            gx = gx < 1 ? 1 : (gx > nunits ? nunits : gx);
+            const int units = (nunits + gx - 1) / gx;               // of the busiest workgroup
+            const double cost = (double)units * ((gps + 7) / 8) * (1.0 + 0.02 * ks);
+            if (cost < best) { best = cost; o.KS = ks; o.gps = gps; o.gx = gx; }
+        }
+    }
+    o.gpw = (o.gps + 7) / 8;
+    o.GP = mbnf4_gp_for(o.gpw);
+    *g = o;
+    return BAGEL_OK;
+}
+
+extern "C" int bagel_gemv_mb_nf4_geometry(int32_t M, int32_t N, int32_t K, int32_t epilogue, int32_t workgroups, int32_t* per, int32_t* slice_groups,
+                                          int32_t* ks, int32_t* gx) {
+    BAGEL_REQUIRE(per && slice_groups && ks && gx, "gemv_mb_nf4_geometry: null pointer");
+    MbNf4Geometry g;
+    if (int rc = mbnf4_plan(M, N, K, epilogue, workgroups, &g)) return rc;
+    *per = g.gpw; *slice_groups = g.gps; *ks = g.KS; *gx = g.gx;
+    return BAGEL_OK;
+}
+
+extern "C" int bagel_gemv_mb_nf4_workspace_bytes(int32_t N, int32_t K, int64_t* bytes) {
+    BAGEL_REQUIRE(bytes && N > 0 && K > 0 && (K % 128) == 0 && (N % 16) == 0, "gemv_mb_nf4_workspace_bytes: bad argument");
+    // an upper bound for every M and workgroup count: the planner tries at most 4 x the minimum slice count, slabs have at most 32 rows
+    const int G = K / 128;
+    *bytes = G <= 8 * MBNF4_MAX_GPW ? 0 : (int64_t)4 * mbnf4_ks_min(G) * 32 * N * 4;
+    return BAGEL_OK;
+}
+
 // Per-phase validation and LDS-ring geometry of the decode engine (engine.hip).
 int eng_geometry(const void* const* ptrs, const int64_t* dims, int n_phases, int n_wg, int want_slots, int waves, int loaders, int depth,
                  EngGeometry* out) {

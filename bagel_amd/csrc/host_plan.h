@@ -76,6 +76,22 @@ BAGEL_HD static inline void mbw4_wave_steps(int gpw, int gps, int nsteps, int sl
 // the shape verdict of bagel_gemv_mb_w4_bf16 on `wgs` workgroups: 0 and the geometry, or the refusal the launcher reports (g is then untouched)
 int mbw4_plan(int M, int N, int K, int epilogue, int wgs, MbW4Geometry* g);
 
+// ---- gemv_mb_nf4.hip: the same stream on NF4 codes.  K is counted in k-groups of 128 weights (64 code bytes per weight row: one 16-byte load per lane, two
+//      absmax blocks); a slice (gridDim.y) takes gps groups, each of its 8 waves gpw of them (GP = 1, 2 or 4 >= gpw fragments per wave: the instantiation) ----
+struct MbNf4Geometry { int GP, gpw, gps, KS, gx, MB; };
+// k-groups [*g0, *g0 + *ng) of wave `wave` of slice `slice` out of the row's G = K / 128 (*ng == 0: the wave has no work): the kernel and the fuzz program share it
+BAGEL_HD static inline void mbnf4_wave_groups(int gpw, int gps, int G, int slice, int wave, int* g0, int* ng) {
+    const int a = slice * gps + wave * gpw;
+    int gend = (slice + 1) * gps;
+    gend = gend < G ? gend : G;
+    int b = a + gpw;
+    b = b < gend ? b : gend;
+    *g0 = a;
+    *ng = a < b ? b - a : 0;
+}
+// the shape verdict of bagel_gemv_mb_nf4_bf16 on `wgs` workgroups: 0 and the geometry, or the refusal the launcher reports (g is then untouched)
+int mbnf4_plan(int M, int N, int K, int epilogue, int wgs, MbNf4Geometry* g);
+
 // ---- engine.hip: per-phase unit form and the LDS ring beside the activation vector and the sync block ----
 #define ENG_MAXPH 4
 #define ENG_MAX_SLOTS 8

@@ -667,7 +667,10 @@ class Bagel(nn.Module):
         or BAGEL_DECODE_GRAPH=0 keeps every step eager).  ``past_key_values`` receives the new K/V rows at the end, as
         the reference's in-place cache update does.  ``weight_quant="int8_rowwise"`` (or ``model.decode_weight_quant``) streams row-wise
         INT8 copies of the layer weights instead of bf16 -- an option that changes results, like the reference's quantised
-        load modes; default off."""
+        load modes; default off.  ``weight_quant="nf4"`` streams bitsandbytes-NF4 codes (the reference's own 4-bit mode): up to 4 requests, and
+        more than 32, on ``gemv_nf4`` (fp32 weight ``code * absmax``, four rows per pass over the codes); 5-32 requests on the weight stream of
+        csrc/gemv_mb_nf4.hip -- one pass for all rows, the weight rounded to bf16 once as ``dequantize_nf4`` does, so the two routes differ by one
+        bf16 rounding per weight (BAGEL_GEMV_MB_NF4=0 keeps 5-32 requests on ``gemv_nf4``)."""
         import os
         from .decode import DecodeSession
         lm = self.language_model

@@ -160,6 +160,13 @@ class DecodeSession:
             raise NotImplementedError("int8 weights need row lengths that are multiples of 16")
         if weight_quant == "nf4" and (eng.H % 64 or eng.I % 64 or (nq * dp) % 64):
             raise NotImplementedError("nf4 weights need row lengths that are multiples of the 64-weight block")
+        self.mb_nf4_ws = None
+        if weight_quant == "nf4" and ops.NF4_GEMV_MAX_ROWS < B <= ops.MB_NF4_MAX_ROWS:
+            # 5..32 requests stream the codes once for all rows (csrc/gemv_mb_nf4.hip); the K-slice workspace of the long rows is the session's own
+            # (a stable pointer for the hipGraph), sized over the four projection shapes
+            shapes = [((nq + 2 * nkv) * dp, eng.H), (eng.H, nq * dp), (2 * eng.I, eng.H), (eng.H, eng.I)]
+            self.mb_nf4_ws = torch.empty(max(max(ops.mb_nf4_workspace_floats(n, k) if k % 128 == 0 and n % 16 == 0 else 0 for n, k in shapes), 4),
+                                         dtype=torch.float32, device=dev)
         if weight_quant == "mxfp4":
             if eng.H % 128 or eng.I % 128 or (nq * dp) % 128:
                 raise NotImplementedError("mxfp4 weights need row lengths that are multiples of 128")
@@ -273,6 +280,15 @@ class DecodeSession:
                     # more than 32 requests, a refused shape or BAGEL_GEMV_MB_W4=0: the large-M kernel (few tiles at these row counts: the correctness fallback)
                     return ops.gemm_w4(aq, sa, w[0], w[1], out, bias=bias, residual=res, epilogue=epi, M=B)
                 if self.weight_quant == "nf4":
+                    bias, res, epi = kw.get("bias"), kw.get("residual"), kw.get("epilogue", ops.EPI_NONE)
+                    if ops.NF4_GEMV_MAX_ROWS < B <= ops.MB_NF4_MAX_ROWS and ops.gemv_mb_nf4_supported(h if norm_w is not None else inp, w[0], w[1], out,
+                                                                                                     bias, res, epi, M=B):
+                        # 5..32 requests: one pass over the codes for all rows on the bf16 MFMA, the RMSNorm as a launch of its own in front
+                        if norm_w is not None:
+                            ops.rmsnorm(inp, norm_w, h, eng.eps)
+                            inp = h
+                        return ops.gemv_mb_nf4(inp, w[0], w[1], out, bias=bias, residual=res, epilogue=epi, M=B, workspace=self.mb_nf4_ws)
+                    # up to 4 requests, more than 32, a refused shape or BAGEL_GEMV_MB_NF4=0: four rows per pass over the codes, the RMSNorm fused
                     return ops.gemv_nf4(inp, w[0], w[1], out, norm_w=norm_w, eps=eng.eps, M=B, **kw)
                 return ops.gemv_w8(inp, w[0], w[1], out, norm_w=norm_w, eps=eng.eps, M=B, **kw)
             if fused:

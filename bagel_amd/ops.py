@@ -491,6 +491,82 @@ def gemv_nf4(A, Wq, absmax, C, *, bias=None, residual=None, epilogue=EPI_NONE, M
     return C
 
 
+NF4_GEMV_MAX_ROWS = 4      # bagel_gemv_nf4_bf16 multiplies at most four activation rows per pass over the codes
+MB_NF4_MAX_ROWS = 32
+_MB_NF4_WS = {}
+
+
+def gemv_mb_nf4_enabled():
+    """BAGEL_GEMV_MB_NF4=0: 5..32 rows on NF4 weights stay on ``gemv_nf4`` (four rows per pass over the codes) instead of the weight stream (same-box A/B of
+    the batched decode step); read per call."""
+    return os.environ.get("BAGEL_GEMV_MB_NF4", "1") != "0"
+
+
+def mb_nf4_workspace_floats(N, K):
+    """fp32 elements of the K-slice workspace bagel_gemv_mb_nf4_bf16 may need for [N, K] NF4 weights at ANY row count (bagel_gemv_mb_nf4_workspace_bytes);
+    0: the row runs in one slice whatever M is."""
+    out = ctypes.c_int64(0)
+    check(lib().bagel_gemv_mb_nf4_workspace_bytes(N, K, ctypes.addressof(out)), "bagel_gemv_mb_nf4_workspace_bytes")
+    return out.value // 4
+
+
+def gemv_mb_nf4_supported(A, Wq, absmax, C, bias, residual, epilogue, M=None):
+    if not gemv_mb_nf4_enabled():
+        return False
+    N, K = Wq.shape[0], Wq.shape[1] * 2
+    M = A.shape[0] if M is None else M
+    if not 1 <= M <= MB_NF4_MAX_ROWS:
+        return False
+    if epilogue == EPI_SWIGLU16 and (bias is not None or residual is not None):
+        return False
+    if K % 64 or absmax.shape != (N, K // 64) or not absmax.is_contiguous():
+        return False
+    ok = A.data_ptr() % 16 == 0 and Wq.data_ptr() % 16 == 0 and _ld(A) % 8 == 0 and Wq.stride(0) % 16 == 0 and C.data_ptr() % 8 == 0 and _ld(C) % 4 == 0
+    ok = ok and (bias is None or bias.data_ptr() % 8 == 0)
+    if not (ok and (residual is None or (residual.data_ptr() % 8 == 0 and _ld(residual) % 4 == 0))):
+        return False
+    # the shape verdict is the launcher's own (it does not depend on the workgroup count; 256 = an MI355X)
+    g = (ctypes.c_int32 * 4)()
+    a = ctypes.addressof(g)
+    return lib().bagel_gemv_mb_nf4_geometry(M, N, K, int(epilogue), 256, a, a + 4, a + 8, a + 12) == 0
+
+
+def gemv_mb_nf4(A, Wq, absmax, C, *, bias=None, residual=None, epilogue=EPI_NONE, M=None, workspace=None):
+    """C[M <= 32, N] = epilogue(A @ dequantize_nf4(Wq, absmax)^T): bf16 activations x NF4 weights as the batched-decode weight stream
+    (bagel_gemv_mb_nf4_bf16): every code is read once for all M rows, de-quantised in registers to bf16(code_book[code] * absmax) -- the weight
+    ``dequantize_nf4`` writes, one bf16 rounding away from ``gemv_nf4``'s fp32 weight -- and multiplied on the bf16 MFMA with fp32 accumulation.  Epilogues
+    none (+bias, +residual) / SwiGLU16; no fused RMSNorm.  Long rows (K > 4096: the 7B down projection) run as K slices through an fp32 workspace
+    (``workspace`` or a per-(device, stream) one) and a second, tiny launch."""
+    _req(A, BF16, "gemv_mb_nf4.A"); _req(Wq, torch.uint8, "gemv_mb_nf4.Wq"); _req(absmax, torch.float32, "gemv_mb_nf4.absmax"); _req(C, BF16, "gemv_mb_nf4.C")
+    N, K = Wq.shape[0], 2 * Wq.shape[1]
+    if A.shape[-1] != K:
+        raise BagelHipError(f"gemv_mb_nf4: A has {A.shape[-1]} columns, Wq holds K={K}")
+    if K % 64 or absmax.shape != (N, K // 64) or not absmax.is_contiguous():
+        raise BagelHipError(f"gemv_mb_nf4: absmax must be a contiguous ({N}, K // 64) tensor, got {tuple(absmax.shape)}")
+    if M is None:
+        M = A.shape[0]
+    if M > A.shape[0] or M > C.shape[0] or (residual is not None and M > residual.shape[0]):
+        raise BagelHipError(f"gemv_mb_nf4: M={M} exceeds the rows of A / C / residual")
+    if residual is not None:
+        _req(residual, BF16, "gemv_mb_nf4.residual")
+    if bias is not None:
+        _req(bias, BF16, "gemv_mb_nf4.bias")
+    # (a shape the launcher refuses gets ITS message, not the workspace query's)
+    need = mb_nf4_workspace_floats(N, K) * 4 if K > 0 and N > 0 and K % 128 == 0 and N % 16 == 0 else 0
+    ws = workspace
+    if need and ws is None:
+        key = _ws_key(A.device)
+        ws = _MB_NF4_WS.get(key)
+        if ws is None or ws.numel() * 4 < need:
+            ws = _MB_NF4_WS[key] = torch.empty(max(need // 4, 1 << 20), dtype=torch.float32, device=A.device)
+    if ws is not None:
+        _req(ws, torch.float32, "gemv_mb_nf4.workspace")
+    check(lib().bagel_gemv_mb_nf4_bf16(_ptr(A), _ld(A), _ptr(Wq), Wq.stride(0), _ptr(absmax), _ptr(bias), _ptr(residual),
+                                       _ld(residual) if residual is not None else 0, _ptr(C), _ld(C), M, N, K, epilogue,
+                                       _ptr(ws) if need else None, ws.numel() * 4 if need else 0, _stream()), "bagel_gemv_mb_nf4_bf16")
+    return C
+
+
 def quantize_rows_mxfp4(W):
     """bf16 [N, K] (K % 128 == 0) -> (u8 [N, K/2] E2M1 codes, two per byte; u8 [N, 16 * ceil(K/512)] E8M0 block scales in device order);
     see bagel_quantize_rows_mxfp4 / oracle/mxfp4.py."""

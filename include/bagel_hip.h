@@ -257,6 +257,26 @@ int bagel_dequantize_rows_i8_bf16(const void* q, int64_t ldq, const float* scale
 int bagel_gemv_nf4_bf16(const void* A, int64_t lda, const void* Wq, int64_t ldw_bytes, const float* absmax, const void* bias,
                         const void* R, int64_t ldr, void* C, int64_t ldc, const void* norm_w, float eps, int32_t M, int32_t N,
                         int32_t K, int32_t epilogue, bagel_stream_t stream);
+/* The NF4 projection for 1..32 rows as a pure weight stream (batched decode on NF4 weights: 5..32 concurrent requests, which bagel_gemv_nf4_bf16 serves
+ * four rows per pass over the codes): C[m, :] = epilogue(sum_k A[m, k] * bf16(code_book[code[n, k]] * absmax[n, k / 64])), A bf16, Wq / absmax exactly as
+ * bagel_quantize_nf4 writes them (absmax contiguous [N, K / 64]).  The weight is rounded to bf16 ONCE, after the fp32 multiply -- bit-equal to
+ * bagel_dequantize_nf4_bf16, what bitsandbytes multiplies with for more than one row -- and the product accumulates in fp32 on mfma_f32_16x16x32_bf16
+ * (bagel_gemv_nf4_bf16 keeps the fp32 weight: the two differ by one bf16 rounding per weight).  bagel_gemv_mb_bf16's form: the 8 waves of a persistent
+ * workgroup partition K in groups of 128 weights and keep their activation fragments in registers (one block of 16 rows, or two); every code byte is loaded
+ * once.  Epilogues none (+bias, +residual; R == C allowed) / SwiGLU16 (3) with the rounding points of bagel_gemv_mb_bf16; no fused RMSNorm.  K % 128 == 0,
+ * N % 16 == 0 (SwiGLU16: N % 32 == 0, no bias / residual); lda in elements (% 8), ldq in bytes (% 16).  Rows longer than 4096 elements run as K slices over
+ * workgroups through a caller-owned fp32 workspace (bagel_gemv_mb_nf4_workspace_bytes: an upper bound for every M and workgroup count; 16-byte aligned;
+ * only touched by this call) and a second small launch.  Deterministic: fixed summation order, no atomics; a row's result does not depend on the other
+ * rows or on M. */
+int bagel_gemv_mb_nf4_workspace_bytes(int32_t N, int32_t K, int64_t* bytes);
+/* The launcher's own shape verdict and launch geometry on `workgroups` persistent workgroups, pure host code: 0 and per = k-groups of 128 weights per
+ * wave (1..4; the instantiation holds 1, 2 or 4), slice_groups = k-groups per K slice, ks = K slices (> 1: workspace needed), gx = workgroups per slice;
+ * or the argument error bagel_gemv_mb_nf4_bf16 would report for this shape. */
+int bagel_gemv_mb_nf4_geometry(int32_t M, int32_t N, int32_t K, int32_t epilogue, int32_t workgroups, int32_t* per, int32_t* slice_groups,
+                               int32_t* ks, int32_t* gx);
+int bagel_gemv_mb_nf4_bf16(const void* A, int64_t lda, const void* Wq, int64_t ldq_bytes, const float* absmax, const void* bias, const void* R,
+                           int64_t ldr, void* C, int64_t ldc, int32_t M, int32_t N, int32_t K, int32_t epilogue, void* workspace,
+                           int64_t workspace_bytes, bagel_stream_t stream);
 
 /* MXFP4 weight-only projections for the decode path: the 4-bit counterpart of the reference's bitsandbytes NF4 load mode
  * (app.py:114-125) on the chip's own block-scaled MFMA operand -- an OPTION that changes results.  OCP-MX FP4: codes E2M1, two per
